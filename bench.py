@@ -14,7 +14,7 @@ env's escalation) follows on a side stream.  Steps rotate over
 `--streams` pipelines (engine + stream each, default 4), so one batch's
 rollout tail overlaps the next batches' work; every step is a whole batch.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--candidates 8192]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--candidates 8192] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 Multi-GPU: weak scaling, one process per GPU, each rank evaluates its own
@@ -22,6 +22,12 @@ Multi-GPU: weak scaling, one process per GPU, each rank evaluates its own
 timing barrier and the max-over-ranks reduction.  Run directly with --gpus N
 (no WORLD_SIZE in the environment), the script starts the N ranks itself as
 child processes before any GPU call; under a launcher, WORLD_SIZE must equal N.
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's
+outputs if --dump-outputs is given and prints the JSON line.  --full adds the
+legs that take runs of their own after the timed region: the drop-in env API
+rate (--e2e-*), the CPU baselines (--cpu-budget) and, with N > 1, rank 0's
+re-evaluation of every rank's block (the shard check).
 """
 import argparse
 import json
@@ -253,6 +259,26 @@ def e2e_api(env, poses, J, h, steps):
     return mask, labels, float(np.median(ts))
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, suffix=""):
+    """write what the last timed step returned as <dirname>/<name><suffix>.npy,
+    float32 (masks) or float64 (everything else: int32 values are exact);
+    a set over DUMP_MAX_BYTES is cut to a fixed seeded sample of candidates"""
+    os.makedirs(dirname, exist_ok=True)
+    out = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype in (np.bool_, np.uint8) else np.float64)
+           for k, v in arrays.items()}
+    n = len(next(iter(out.values())))
+    per_cand = sum(a.nbytes for a in out.values()) / max(1, n)
+    if per_cand * n > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, int(DUMP_MAX_BYTES // (per_cand + 8)), replace=False))
+        out = {k: np.ascontiguousarray(a[keep]) for k, a in out.items()}
+        out["sample_index"] = keep.astype(np.float64)
+    for k, a in out.items():
+        np.save(os.path.join(dirname, k + suffix + ".npy"), a)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -287,15 +313,23 @@ def main():
     ap.add_argument("--candidates", type=int, default=8192)
     ap.add_argument("--horizon", default="h200")
     ap.add_argument("--solver", default=None, help="override the model's solver (Newton | PGS)")
-    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU baseline work (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the drop-in env API legs (--e2e-*), the CPU baselines "
+                         "(--cpu-budget) and, with N > 1, the shard check; a plain run skips them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (collision_free, label, fail_step, obj_qpos, stats; "
+                         "escalated candidates merged) as DIR/<name>.npy (rank r > 0 of N > 1: <name>.rank<r>.npy)")
+    ap.add_argument("--cpu-budget", type=float, default=15.0,
+                    help="--full: seconds of CPU baseline work (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="CPU baseline threads (default: the CPUs this process may use, cgroup quota included)")
     ap.add_argument("--no-shard-check", dest="shard_check", action="store_false",
-                    help="N > 1: skip rank 0's single-GPU re-evaluation of every rank's block")
+                    help="--full, N > 1: skip rank 0's single-GPU re-evaluation of every rank's block")
     ap.add_argument("--e2e-large", type=int, default=8,
-                    help="also time the drop-in API on the batch repeated this many times in one call (0 = skip)")
+                    help="--full: also time the drop-in API on the batch repeated this many times in one call "
+                         "(0 = skip)")
     ap.add_argument("--e2e-steps", type=int, default=5,
-                    help="batches timed through the drop-in env API on host arrays (0 = skip)")
+                    help="--full: batches timed through the drop-in env API on host arrays (0 = skip)")
     ap.add_argument("--e2e-slices", type=int, default=None,
                     help="time slices by relaunch of the env API's rollout calls (default: the env's SLICES)")
     ap.add_argument("--e2e-yield", type=int, default=None,
@@ -588,12 +622,21 @@ def main():
     labels = d_label.cpu().numpy().astype(bool)
     fail = d_fail.cpu().numpy()
     stats = d_stats.cpu().numpy()
+    if args.dump_outputs:
+        # the last timed step ran on pipeline (K - 1) % S; merge_last() above
+        # put its escalated candidates' results in place
+        PL = pipes[(args.steps - 1) % len(pipes)]
+        dump_outputs(args.dump_outputs,
+                     {"collision_free": PL.free.cpu().numpy(), "label": PL.label.cpu().numpy(),
+                      "fail_step": PL.fail.cpu().numpy(), "obj_qpos": PL.objq.cpu().numpy(),
+                      "stats": PL.stats.cpu().numpy()},
+                     suffix=f".rank{rank}" if rank else "")
     e2e = None
     if args.e2e_slices is not None:
         env.SLICES = args.e2e_slices
     if args.e2e_yield is not None:
         env.YIELD_EVERY = args.e2e_yield
-    if args.e2e_steps > 0:
+    if args.full and args.e2e_steps > 0:
         # the env's engines are created once per env (as a CLI run creates them
         # once): one untimed call builds the small-call engine
         # (GravitylessObjectGrasping.engine_for_rollouts) before the timed ones
@@ -622,7 +665,7 @@ def main():
                "rollout_engine": ("G rows in LDS" if env.engine_for_rollouts(int(free.sum())) is not env.engine
                                   else "G rows in HBM" if int(env.engine.desc.g_rows_hbm) else "G rows in LDS")}
     shard_check = None
-    if world > 1 and args.shard_check:
+    if args.full and world > 1 and args.shard_check:
         # the global candidate set is the concatenation of the
         # seed-b blocks (rank b evaluates block b); rank 0 re-evaluates every
         # block on its own GPU and compares the gathered labels bit for bit
@@ -672,7 +715,7 @@ def main():
                                f"{args.horizon} close-lift-shake rollout ({horizon} steps, dt 1 ms)",
                    "candidates_per_gpu": N, "horizon_steps": horizon, "solver": env.model.options.get("solver"),
                    "parallelism": f"batch split x{world}", "streams": len(pipes),
-                   "yield_every": int(args.yield_every)},
+                   "yield_every": int(args.yield_every), "full": bool(args.full)},
         "detail": {"collision_free": int(free.sum()), "stable": int(labels.sum()),
                    "rollouts_per_s": float(free.sum()) * world * args.steps / dt,
                    "host_enqueue_s": t_enq,
@@ -719,7 +762,7 @@ def main():
                              "re-runs are mgs_special_rollout_esc in a trace"},
         "cpu_baseline": None,
     }
-    if world == 1 and args.cpu_budget > 0:
+    if args.full and world == 1 and args.cpu_budget > 0:
         cb = cpu_baseline(env, poses, J, h, args.cpu_budget, args.cpu_threads)
         n = cb["n"]
         agree = bool(np.array_equal(cb["free"], free[:n]) and np.array_equal(cb["labels"], labels[:n]))

@@ -8,8 +8,8 @@
 #   tests     the GPU suite (pytest -m gpu)
 #   tk:<expr> the GPU tests matching a pytest -k expression
 #   smoke     __graft_entry__.smoke()
-#   bench     the driver's command, `bench.py --gpus 1 --steps 20 --warmup 5`
-#             (full line: e2e API, CPU baseline); first process of the call
+#   bench     the driver's command, `bench.py --gpus 1 --steps 20 --warmup 5`,
+#             with --full (e2e API, CPU baseline); first process of the call
 #   rep       the driver's command without CPU baseline / e2e, 3 processes
 #   api       the drop-in env API per call, one rollout launch vs 4 time slices
 #   rot       in-launch rotation A/B (bench --yield-every, env API --e2e-yield)
@@ -69,7 +69,7 @@ for step in "$@"; do
       timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || fail smoke $O/smoke.log
       tail -1 $O/smoke.log ;;
     bench)
-      timeout -k 10 600 python3 $DRIVER > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
+      timeout -k 10 600 python3 $DRIVER --full > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
       summ $O/bench.json ;;
     rep)
       for r in 1 2 3; do
@@ -79,7 +79,7 @@ for step in "$@"; do
     api)
       # the drop-in env API per 8192-candidate call: one rollout launch vs time slices
       for sl in 1 4; do
-        timeout -k 10 300 python3 $DRIVER --cpu-budget 0 --e2e-steps 4 --e2e-slices $sl > $O/api$sl.json \
+        timeout -k 10 300 python3 $DRIVER --full --cpu-budget 0 --e2e-steps 4 --e2e-slices $sl > $O/api$sl.json \
           2> $O/api$sl.err || fail api $O/api$sl.err
         summ $O/api$sl.json
       done ;;
@@ -92,7 +92,7 @@ for step in "$@"; do
         summ $O/rot$y.json
       done
       for y in 0 32; do
-        timeout -k 10 300 python3 $DRIVER --cpu-budget 0 --e2e-steps 4 --e2e-yield $y > $O/apiy$y.json \
+        timeout -k 10 300 python3 $DRIVER --full --cpu-budget 0 --e2e-steps 4 --e2e-yield $y > $O/apiy$y.json \
           2> $O/apiy$y.err || fail rot $O/apiy$y.err
         summ $O/apiy$y.json
       done ;;
@@ -104,7 +104,7 @@ for step in "$@"; do
         summ $O/streams$k.json
       done ;;
     n2)
-      timeout -k 10 300 python3 bench.py --gpus 2 --steps 3 --warmup 1 --cpu-budget 0 --e2e-steps 0 \
+      timeout -k 10 300 python3 bench.py --gpus 2 --steps 3 --warmup 1 --full --cpu-budget 0 --e2e-steps 0 \
         > $O/n2.json 2> $O/n2.err || fail n2 $O/n2.err
       summ $O/n2.json ;;
     trace)
