@@ -3096,11 +3096,12 @@ DEVI void mccd_perturb(const Dat& d, Dat& dw, int g1, int g2, const double* n, c
 
 // multiccd's four perturbed MPRs of a pair that multiccd_q cannot take (a hull
 // of more than 8 vertices, or a cylinder: the gripper's link meshes on the
-// object), in lockstep on four 16-lane groups as there (ccd_mpr_q), each
-// support of the four perturbations computed by the whole wave in turn
-// (support_pair over the pair's hulls, the group's perturbed poses from LDS,
-// only for the groups still running): four MPR scalar chains at once instead
-// of one after another, the same supports, the same contacts in the same order
+// object), in lockstep on four 16-lane groups as there (ccd_mpr_q): four MPR
+// scalar chains at once instead of one after another, the same supports, the
+// same contacts in the same order.  PairCtxW (MGS_MCCD_G 0): each support of
+// the four perturbations computed by the whole wave in turn (support_pair over
+// the pair's hulls, the group's perturbed poses from LDS, only for the groups
+// still running); PairCtxG below (the default): by the group itself
 #ifndef MGS_MCCD_W
 #define MGS_MCCD_W 1   // 0: these perturbations one after another (A/B builds)
 #endif
@@ -3135,18 +3136,172 @@ DEVI void mink_support(const PairCtxW& c, const double* dir, SupPt* p, unsigned 
   }
   sub3(p->v, p->a, p->b);
 }
+// The same lockstep MPRs with group-local supports (1, default): every group
+// scans the pair's hulls itself with its 16 lanes, for its own direction and
+// pose, so a lockstep pass is one support call for all four groups instead of
+// up to four whole-wave calls that each load the same vertices again.  Lane li
+// of a group visits vertices li, li + 16, ... in ascending order with a strict
+// '>' (the lowest index of a lane's maxima), the value is max-reduced over the
+// group's DPP row, and the oracle's first maximal vertex is the smallest index
+// among the lanes holding that value: a min-reduction over the row, not the
+// lowest tied lane (lane 1 may hold vertex 17 while lane 2 holds vertex 2) and
+// not a loop over the tied lanes (it would diverge between groups, see
+// ccd_mpr_q).  The context is per lane throughout (hulls, counts, radii and
+// cylinder sizes as well as the pose), so a group could hold a pair of its
+// own; only nmax1 / nmax2, the bounds of the scan loops, are uniform.
+#ifndef MGS_MCCD_G
+#define MGS_MCCD_G 1   // 0: each group's supports by the whole wave in turn (PairCtxW; A/B builds)
+#endif
+#ifndef GS_CH
+#define GS_CH 4          // vertices per lane and batch: 3 GS_CH loads issued before the first compare
+#endif
+struct PairCtxG {
+  int n1, n2;            // the group's vertex counts
+  int nmax1, nmax2;      // the largest count of any group, per side (uniform: the scan loops' bounds)
+  const double *V1, *V2;
+  double c1[3], c2[3];   // the lane's vertex of a hull of at most 16 vertices (lane & 15 < n)
+  double r1, r2;         // rounding radii
+  double cy1[2], cy2[2];   // cylinder radius / half-height
+  const double* pose;    // the group's perturbed pose in LDS (R1 R2 x1 x2)
+  double cx1[3], cx2[3];   // its perturbed centres
+};
+DEVI void pair_ctxg(const Mdl& md, int g1, int g2, const double* pose, PairCtxG& c) {
+  const int li = lane_id() & 15;
+  const int32_t *ghull = IA(md, geom_hullid), *hadr = IA(md, hull_vertadr), *hnum = IA(md, hull_vertnum);
+  const int h1 = ghull[g1], h2 = ghull[g2];
+  c.n1 = hnum[h1];
+  c.n2 = hnum[h2];
+  c.nmax1 = c.n1;
+  c.nmax2 = c.n2;
+  c.V1 = DA(md, hull_vert) + 3 * hadr[h1];
+  c.V2 = DA(md, hull_vert) + 3 * hadr[h2];
+  const int i1 = li < c.n1 ? li : 0, i2 = li < c.n2 ? li : 0;
+#pragma unroll
+  for (int k = 0; k < 3; k++) { c.c1[k] = c.V1[k * c.n1 + i1]; c.c2[k] = c.V2[k * c.n2 + i2]; }
+  c.r1 = DA(md, geom_radius)[g1];
+  c.r2 = DA(md, geom_radius)[g2];
+  const double* cy = DA(md, geom_cyl);
+  c.cy1[0] = cy[2 * g1]; c.cy1[1] = cy[2 * g1 + 1];
+  c.cy2[0] = cy[2 * g2]; c.cy2[1] = cy[2 * g2 + 1];
+  c.pose = pose;
+#pragma unroll
+  for (int k = 0; k < 3; k++) { c.cx1[k] = pose[18 + k]; c.cx2[k] = pose[21 + k]; }
+}
+DEVI void mpr_centres(const PairCtxG& c, const Dat&, int, int, double* a, double* b) {
+#pragma unroll
+  for (int k = 0; k < 3; k++) { a[k] = c.cx1[k]; b[k] = c.cx2[k]; }
+}
+DEVI int dpp_i(int x, int ctrl_sel) {
+  switch (ctrl_sel) {
+    case 0: return __builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, false);
+    case 1: return __builtin_amdgcn_mov_dpp(x, 0x4E, 0xF, 0xF, false);
+    case 2: return __builtin_amdgcn_mov_dpp(x, 0x141, 0xF, 0xF, false);
+    default: return __builtin_amdgcn_mov_dpp(x, 0x140, 0xF, 0xF, false);
+  }
+}
+// the group's support vertex of one hull along dl (geom frame, uniform within
+// the group): oracle support_geom's hull scan.  n, V, cached and dl are the
+// group's; nmax bounds the loop for every group.  Every DPP level is an
+// exchange inside the row, so all 16 lanes end up with the row's maximum.
+DEVI void sup_group(int n, int nmax, const double* V, const double* cached, const double* dl, double* v) {
+  const int lane = lane_id(), li = lane & 15;
+  SupAcc a;
+  sup_init(a);
+  if (nmax <= 16) {
+    if (li < n) {
+      double sc = (cached[0] * dl[0] + cached[1] * dl[1]) + cached[2] * dl[2];
+      if (sc > a.best) { a.best = sc; a.bi = li; a.vx = cached[0]; a.vy = cached[1]; a.vz = cached[2]; }
+    }
+  } else {
+#pragma unroll 1
+    for (int base = 0; base < nmax; base += GS_CH * 16) {
+      double x[GS_CH], y[GS_CH], z[GS_CH];
+#pragma unroll
+      for (int u = 0; u < GS_CH; u++) {
+        const int i = base + u * 16 + li;
+        const int ii = i < n ? i : 0;
+        x[u] = V[ii]; y[u] = V[n + ii]; z[u] = V[2 * n + ii];
+      }
+#pragma unroll
+      for (int u = 0; u < GS_CH; u++) {
+        const int i = base + u * 16 + li;
+        double sc = (x[u] * dl[0] + y[u] * dl[1]) + z[u] * dl[2];
+        if (i < n && sc > a.best) { a.best = sc; a.bi = i; a.vx = x[u]; a.vy = y[u]; a.vz = z[u]; }
+      }
+    }
+  }
+  // (all four levels whatever the count: every lane of the group needs the
+  // result, also the lanes past a small hull's vertices)
+  double m = a.best;
+  m = max_f64(m, dpp_d(m, 0));
+  m = max_f64(m, dpp_d(m, 1));
+  m = max_f64(m, dpp_d(m, 2));
+  m = max_f64(m, dpp_d(m, 3));
+  // the smallest index among the lanes that hold the maximum (a lane that took
+  // no vertex keeps 0x7fffffff); none (as sup_finish): the group's first lane
+  int w = a.best == m ? a.bi : 0x7fffffff, t;
+  t = dpp_i(w, 0); w = t < w ? t : w;
+  t = dpp_i(w, 1); w = t < w ? t : w;
+  t = dpp_i(w, 2); w = t < w ? t : w;
+  t = dpp_i(w, 3); w = t < w ? t : w;
+  if (w == 0x7fffffff) w = 0;
+  const int src = (lane - li) + (w & 15);
+  v[0] = shfl(a.vx, src);
+  v[1] = shfl(a.vy, src);
+  v[2] = shfl(a.vz, src);
+}
+// support_pair for every group at once: dir, the pose and the results are the
+// group's (the same expressions as support_pair)
+DEVI void support_pairg(const PairCtxG& c, const double* dir, double* out1, double* out2) {
+  const double* P = c.pose;
+  double nd[3] = {-dir[0], -dir[1], -dir[2]};
+  double R[9], dl[3], v[3], t[3], x[3];
+#pragma unroll
+  for (int k = 0; k < 9; k++) R[k] = P[k];
+  mulmtv3(dl, R, dir);
+  sup_group(c.n1, c.nmax1, c.V1, c.c1, dl, v);
+  if (c.cy1[0] > 0.0) cyl_support(v, c.cy1, dl);
+#pragma unroll
+  for (int k = 0; k < 3; k++) x[k] = P[18 + k];
+  mulmv3(t, R, v);
+  add3(out1, x, t);
+  if (c.r1 > 0.0) { out1[0] = out1[0] + c.r1 * dir[0]; out1[1] = out1[1] + c.r1 * dir[1]; out1[2] = out1[2] + c.r1 * dir[2]; }
+#pragma unroll
+  for (int k = 0; k < 9; k++) R[k] = P[9 + k];
+  mulmtv3(dl, R, nd);
+  sup_group(c.n2, c.nmax2, c.V2, c.c2, dl, v);
+  if (c.cy2[0] > 0.0) cyl_support(v, c.cy2, dl);
+#pragma unroll
+  for (int k = 0; k < 3; k++) x[k] = P[21 + k];
+  mulmv3(t, R, v);
+  add3(out2, x, t);
+  if (c.r2 > 0.0) { out2[0] = out2[0] + c.r2 * nd[0]; out2[1] = out2[1] + c.r2 * nd[1]; out2[2] = out2[2] + c.r2 * nd[2]; }
+}
+DEVI void mink_support(const PairCtxG& c, const double* dir, SupPt* p, unsigned long long) {
+  PT(4);
+  PCNT(28, 1);
+  PCNT(29, (c.n1 > WAVE) + (c.n2 > WAVE));
+  support_pairg(c, dir, p->a, p->b);
+  sub3(p->v, p->a, p->b);
+  if (c.n1 > WAVE || c.n2 > WAVE) PT(39); else PT(22);
+}
 DEVI void multiccd_w(const Mdl& md, Dat& d, int pair, int g1, int g2, const double* n, const double* pos) {
   mccd_list_init(d, pos);
 #pragma unroll 1
   for (int q = 0; q < 4; q++) mccd_perturb(d, d, g1, g2, n, pos, q, MCCD_POSEW + 24 * q);
   const int lane = lane_id(), grp = lane >> 4;
   {
+#if MGS_MCCD_G
+    PairCtxG pc;
+    pair_ctxg(md, g1, g2, (const double*)d.poly + MCCD_POSEW + 24 * grp, pc);
+#else
     PairCtxW pc;
     pair_ctx(md, d, g1, g2, pc.base);
     pc.pose = (const double*)d.poly + MCCD_POSEW;
     const double* P = pc.pose + 24 * grp;
 #pragma unroll
     for (int k = 0; k < 3; k++) { pc.cx1[k] = P[18 + k]; pc.cx2[k] = P[21 + k]; }
+#endif
     double nn[3], dd = 0.0, pp[3], dir[3] = {0.0, 0.0, 0.0};
     const int hit = ccd_mpr_q(md, d, pc, nn, &dd, pp);
     if ((lane & 15) == 0) mccd_store(d, MCCD_RES + 12 * grp, hit, nn, pp, dir, dd, -1.0);

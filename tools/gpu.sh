@@ -35,7 +35,7 @@ O=gpurun_out/$TAG
 mkdir -p "$O"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 DRIVER="bench.py --gpus 1 --steps 20 --warmup 5"
-P1="bench.py --streams 1 --steps 1 --warmup 0 --cpu-budget 0 --e2e-steps 0 --no-escalate --fused 0"
+P1="bench.py --streams 1 --steps 1 --warmup 0 --cpu-budget 0 --e2e-steps 0 --no-escalate --fused 1"
 
 summ() {   # one-line summary of a bench JSON line
   python3 - "$1" <<'EOF'

@@ -34,8 +34,12 @@ def rows(path, kernels=("mgs_special_rollout", "mgs_rollout_kernel")):
 def _commit():
     import subprocess
     try:
-        return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True,
+        head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True,
                               text=True, timeout=30).stdout.strip() or None
+        # kernel sources that differ from HEAD: the pass measured the working tree
+        dirty = subprocess.run(["git", "-C", ROOT, "status", "--porcelain", "--", "mj-grasp-sim_amd/csrc", "include"],
+                               capture_output=True, text=True, timeout=30).stdout.strip()
+        return head + " + uncommitted kernel changes" if head and dirty else head
     except (OSError, subprocess.SubprocessError):
         return None
 
@@ -78,7 +82,7 @@ def main(d, tag="r03"):
     if os.path.isfile(kt):
         main_launch_stats(kt, os.path.join(PROF, f"{tag}_rocprof_main_launches.txt"))
     out = {"source": "rocprofv3 --kernel-trace --pmc <counters> (separate passes) on `python3 bench.py --streams 1 "
-                     "--steps 1 --warmup 0 --cpu-budget 0 --e2e-steps 0 --no-escalate --fused 0` (tools/gpu.sh pmc, "
+                     "--steps 1 --warmup 0 --cpu-budget 0 --e2e-steps 0 --no-escalate --fused 1` (tools/gpu.sh pmc, "
                      f"{tag}); "
                      "per rollout dispatch",
            "kernel": "mgs_special_rollout (code object specialised to the headline model)",
