@@ -2872,12 +2872,14 @@ DEVI void mink_support(const PairCtxQ<HW>& c, const double* dir, SupPt* p, unsig
 #define MQ_FIN 5
 #define MQ_DONE 6
 template <class QC>
-DEVI int ccd_mpr_q(const Mdl& md, const Dat& d, const QC& pc, double* n, double* depth, double* pos) {
+DEVI int ccd_mpr_q(const Mdl& md, const Dat& d, const QC& pc, double* n, double* depth, double* pos, int done0 = 0) {
   const double tol = md.m.mpr_tolerance;
   const int maxit = md.m.ccd_iterations;
   SupPt p0, p1, p2, p3, ps;
   double dir[3];
-  int ph = MQ_P1, it = 0, hit = 0;
+  // done0 (per lane): the lane's group has no MPR to run (multiccd_x's empty
+  // and missed slots) -- it starts done, never keeps the loop running, no hit
+  int ph = done0 ? MQ_DONE : MQ_P1, it = 0, hit = 0;
   mpr_centres(pc, d, 0, 0, p0.a, p0.b);
   sub3(p0.v, p0.a, p0.b);
   if (ccd_vzero(p0.v)) p0.v[0] = p0.v[0] + CCD_EPS * 10.0;
@@ -2998,6 +3000,14 @@ DEVI int ccd_mpr_q(const Mdl& md, const Dat& d, const QC& pc, double* n, double*
 #define MCCD_N 40
 #define MCCD_RES 48
 #define MCCD_RES2 96
+// multiccd_x (below): the first MPRs' results of a round's up to four pairs
+// (MCCD_XRES1 + 12 slot) and their perturbed MPRs' (MCCD_XRES + 12 (4 slot +
+// perturbation)), past what the colliders that may run between a pair's
+// stages write (collide_boxbox below 144, multiccd_q / the two-pair MPR below
+// 120, multiccd_w's poses below MCCD_POSEW + 96 = 224); K_POLY_POINTS * 3 = 552
+#define MCCD_XRES1 224
+#define MCCD_XRES 272
+static_assert(MCCD_XRES + 16 * 12 <= K_POLY_POINTS * 3, "multiccd_x results past the polygon scratch");
 DEVI void mccd_store(Dat& d, int at, int hit, const double* n, const double* pos, const double* cd, double depth,
                      double cm) {
   double* o = (double*)d.poly + at;
@@ -3007,14 +3017,16 @@ DEVI void mccd_store(Dat& d, int at, int hit, const double* n, const double* pos
   o[10] = cm;
   o[11] = hit ? 1.0 : 0.0;
 }
-// each group's MPR result (multiccd_q's and multiccd_w's, MCCD_RES + 12 group)
-// taken in perturbation order: distinct ones added to the pair's contacts
-DEVI void mccd_take_groups(const Mdl& md, Dat& d, int pair, int g1, int g2, int ngroups, int& nc) {
+// each group's MPR result (multiccd_q's and multiccd_w's at MCCD_RES + 12 group,
+// multiccd_x's of one pair at MCCD_XRES + 48 slot + 12 group) taken in
+// perturbation order: distinct ones added to the pair's contacts
+DEVI void mccd_take_groups(const Mdl& md, Dat& d, int pair, int g1, int g2, int ngroups, int& nc,
+                           int at = MCCD_RES) {
   const double* cp = (const double*)d.poly;
   const int ncmax = md.m.ncon_max;
 #pragma unroll 1
   for (int k = 0; k < ngroups; k++) {
-    const double* r = cp + MCCD_RES + 12 * k;
+    const double* r = cp + at + 12 * k;
     if (r[11] == 0.0) continue;
     double pk[3] = {r[3], r[4], r[5]};
     if (!mccd_is_new(d, nc, pk, mccd_tol(md, g1, g2))) continue;
@@ -3311,14 +3323,200 @@ DEVI void multiccd_w(const Mdl& md, Dat& d, int pair, int g1, int g2, const doub
   mccd_take_groups(md, d, pair, g1, g2, 4, nc);
 }
 
+// multiccd's perturbed MPRs of up to four pairs at once (multiccd_q<8>'s
+// pairs: kind CONVEX, both hulls of at most 8 vertices, no cylinder): 16
+// groups of 4 lanes in one lockstep ccd_mpr_q call, group g running
+// perturbation g & 3 of the pair in slot g >> 2 -- one chain of passes for
+// the round instead of one per pair.  collision() runs the round's first MPRs
+// beforehand (their results at MCCD_XRES1 + 12 slot) and emits each pair's
+// contacts afterwards in pair order from the results stored here.
+#ifndef MGS_MCCD_X
+#define MGS_MCCD_X 1   // 0: every pair's multiccd on its own (multiccd_q<8>; A/B builds)
+#endif
+// The context is per lane throughout.  Lane li = lane & 3 of a group holds
+// vertices li and li + 4 of both hulls and scans them in ascending order with
+// a strict '>'; the maximum is reduced over the quad (the two quad_perm DPP
+// levels) and the oracle's first maximal vertex is the smallest index among
+// the lanes holding it, by a min-reduction over the quad as in sup_group
+// (lane 0 may hold vertex 4 while lane 1 holds vertex 1).
+#ifndef MGS_MCCD_XV
+#define MGS_MCCD_XV 1   // 0: the lane's vertices read again at every support (A/B builds)
+#endif
+struct PairCtxX {
+  int n1, n2;                    // the group's vertex counts
+  double R1[9], R2[9], x1[3], x2[3];   // its perturbed poses (x1, x2: also the MPR's centres)
+#if MGS_MCCD_XV
+  double v1[2][3], v2[2][3];     // the lane's two vertices of either hull
+#else
+  const double *v1, *v2;         // the hulls' vertices
+#endif
+  double r1, r2;                 // rounding radii
+};
+// one geom's pose turned about the first contact pv (pair_ctxq's expressions)
+DEVI void xpose(const Dat& d, int g, const double* qq, const double* pv, double* R, double* x) {
+  double M[9], Rg[9], xg[3], r[3], t[3];
+  quat2mat(M, qq);
+#pragma unroll
+  for (int k = 0; k < 9; k++) Rg[k] = d.geom_xmat[9 * g + k];
+#pragma unroll
+  for (int k = 0; k < 3; k++) xg[k] = d.geom_xpos[3 * g + k];
+  mulmm3(R, M, Rg);
+  sub3(r, xg, pv);
+  mulmv3(t, M, r);
+  add3(x, t, pv);
+}
+// pair: the lane's pair; n0 / pv: its first contact's normal and position; q: the lane's perturbation
+DEVI void pair_ctxx(const Mdl& md, const Dat& d, int pair, const double* n0, const double* pv, int q, PairCtxX& c) {
+  const int li = lane_id() & 3;
+  const int g1 = IA(md, pair_geom1)[pair], g2 = IA(md, pair_geom2)[pair];
+  const int32_t *ghull = IA(md, geom_hullid), *hadr = IA(md, hull_vertadr), *hnum = IA(md, hull_vertnum);
+  const int h1 = ghull[g1], h2 = ghull[g2];
+  c.n1 = hnum[h1];
+  c.n2 = hnum[h2];
+  const double* V1 = DA(md, hull_vert) + 3 * hadr[h1];
+  const double* V2 = DA(md, hull_vert) + 3 * hadr[h2];
+#if MGS_MCCD_XV
+#pragma unroll
+  for (int u = 0; u < 2; u++) {
+    const int i = li + 4 * u;
+    const int i1 = i < c.n1 ? i : 0, i2 = i < c.n2 ? i : 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { c.v1[u][k] = V1[k * c.n1 + i1]; c.v2[u][k] = V2[k * c.n2 + i2]; }
+  }
+#else
+  c.v1 = V1;
+  c.v2 = V2;
+#endif
+  c.r1 = DA(md, geom_radius)[g1];
+  c.r2 = DA(md, geom_radius)[g2];
+  const int ax = q >> 1, sg = q & 1;
+  double t1[3], t2[3];
+  make_frame(n0, t1, t2);
+  double axis[3] = {ax ? t2[0] : t1[0], ax ? t2[1] : t1[1], ax ? t2[2] : t1[2]};
+  double s = sg ? MCCD_S : -MCCD_S;
+  double qa[4] = {MCCD_C, axis[0] * s, axis[1] * s, axis[2] * s};
+  double qb[4] = {MCCD_C, -(axis[0] * s), -(axis[1] * s), -(axis[2] * s)};
+  xpose(d, g1, qa, pv, c.R1, c.x1);
+  xpose(d, g2, qb, pv, c.R2, c.x2);
+}
+DEVI void mpr_centres(const PairCtxX& c, const Dat&, int, int, double* a, double* b) {
+#pragma unroll
+  for (int k = 0; k < 3; k++) { a[k] = c.x1[k]; b[k] = c.x2[k]; }
+}
+// the quad's support vertex of one hull along dl (geom frame, uniform within
+// the quad): oracle support_geom's hull scan
+#if MGS_MCCD_XV
+DEVI void sup_quad(int n, const double (*V)[3], const double* dl, double* v) {
+  const int lane = lane_id(), li = lane & 3;
+#else
+DEVI void sup_quad(int n, const double* Vg, const double* dl, double* v) {
+  const int lane = lane_id(), li = lane & 3;
+  double V[2][3];
+#pragma unroll
+  for (int u = 0; u < 2; u++) {
+    const int i = li + 4 * u < n ? li + 4 * u : 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) V[u][k] = Vg[k * n + i];
+  }
+#endif
+  SupAcc a;
+  sup_init(a);
+#pragma unroll
+  for (int u = 0; u < 2; u++) {
+    const int i = li + 4 * u;
+    double sc = (V[u][0] * dl[0] + V[u][1] * dl[1]) + V[u][2] * dl[2];
+    if (i < n && sc > a.best) { a.best = sc; a.bi = i; a.vx = V[u][0]; a.vy = V[u][1]; a.vz = V[u][2]; }
+  }
+  double m = a.best;
+  m = max_f64(m, dpp_d(m, 0));
+  m = max_f64(m, dpp_d(m, 1));
+  // the smallest index among the lanes that hold the maximum (sup_group)
+  int w = a.best == m ? a.bi : 0x7fffffff, t;
+  t = dpp_i(w, 0); w = t < w ? t : w;
+  t = dpp_i(w, 1); w = t < w ? t : w;
+  if (w == 0x7fffffff) w = 0;
+  const int src = (lane - li) + (w & 3);
+  v[0] = shfl(a.vx, src);
+  v[1] = shfl(a.vy, src);
+  v[2] = shfl(a.vz, src);
+}
+// support_pair for every quad at once (support_pairq's expressions)
+DEVI void support_pairx(const PairCtxX& c, const double* dir, double* out1, double* out2) {
+  double nd[3] = {-dir[0], -dir[1], -dir[2]};
+  double dl[3], v[3], t[3];
+  mulmtv3(dl, c.R1, dir);
+  sup_quad(c.n1, c.v1, dl, v);
+  mulmv3(t, c.R1, v);
+  add3(out1, c.x1, t);
+  if (c.r1 > 0.0) { out1[0] = out1[0] + c.r1 * dir[0]; out1[1] = out1[1] + c.r1 * dir[1]; out1[2] = out1[2] + c.r1 * dir[2]; }
+  mulmtv3(dl, c.R2, nd);
+  sup_quad(c.n2, c.v2, dl, v);
+  mulmv3(t, c.R2, v);
+  add3(out2, c.x2, t);
+  if (c.r2 > 0.0) { out2[0] = out2[0] + c.r2 * nd[0]; out2[1] = out2[1] + c.r2 * nd[1]; out2[2] = out2[2] + c.r2 * nd[2]; }
+}
+DEVI void mink_support(const PairCtxX& c, const double* dir, SupPt* p, unsigned long long) {
+  PT(4);
+  PCNT(28, 1);
+  support_pairx(c, dir, p->a, p->b);
+  sub3(p->v, p->a, p->b);
+  PT(22);
+}
+// xall: the round's pairs (bits of the batch at c0, slot = rank of the bit).
+// Runs the perturbed MPRs of the slots whose first MPR hit, if there are at
+// least two, and stores the 16 results; returns whether it ran.
+DEVI int multiccd_x(const Mdl& md, Dat& d, int c0, unsigned long long xall) {
+  const int lane = lane_id(), slot = lane >> 4;
+  const double* cp = (const double*)d.poly;
+  int pair = -1;
+  {
+    unsigned long long t = xall;
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+      if (!t) break;
+      const int b = __ffsll((long long)t) - 1;
+      t &= t - 1ull;
+      if (slot == s) pair = c0 + b;
+    }
+  }
+  const int live = pair >= 0 && cp[MCCD_XRES1 + 12 * slot + 11] != 0.0;
+  const unsigned long long lm = __ballot(live);
+  if (__popcll(lm) < 2 * 16) return 0;
+  // the lanes of an empty or missed slot: a live slot's data, and no MPR
+  const int fl = __ffsll((long long)lm) - 1;
+  const int ps = live ? pair : __builtin_amdgcn_readlane(pair, fl);
+  const double* r = cp + MCCD_XRES1 + 12 * (live ? slot : fl >> 4);
+  {
+    double n0[3] = {r[0], r[1], r[2]}, pv[3] = {r[3], r[4], r[5]};
+    PairCtxX pc;
+    pair_ctxx(md, d, ps, n0, pv, (lane >> 2) & 3, pc);
+    double nn[3] = {0.0, 0.0, 0.0}, dd = 0.0, pp[3] = {0.0, 0.0, 0.0}, dir[3] = {0.0, 0.0, 0.0};
+    const int hit = ccd_mpr_q(md, d, pc, nn, &dd, pp, !live);
+    if ((lane & 3) == 0) mccd_store(d, MCCD_XRES + 12 * (lane >> 2), hit, nn, pp, dir, dd, -1.0);
+    wsync();
+  }
+  return 1;
+}
+
 // convex pairs (ccd_mode 1 / 2; oracle collide_convex_mj): one pair on the
 // whole wave, or two pairs whose hulls fit 16-lane rows at once on the two
 // halves (pairB >= 0); then per pair in order its certificate, first contact
 // and multiccd -- four perturbed MPRs on 16-lane groups when both hulls have
 // at most 8 vertices and no cylinder, else one after another through the
 // whole-wave MPR call site the single pair's first MPR uses (each MPR
-// instance inlined once: more copies spilled the eight-per-CU object)
-DEVI void collide_convex_mj(const Mdl& md, Dat& d, int pairA, int pairB, int mccd) {
+// instance inlined once: more copies spilled the eight-per-CU object).
+// collision() has one call site for all of it and splits the pairs of a
+// multiccd_x round (slots xslot, xslot + 1) into stages by xmode:
+//   CX_ALL    first MPR, certificate, first contact and multiccd (every other pair)
+//   CX_FIRST  the first MPR(s) only, results to MCCD_XRES1 + 12 slot
+//   CX_EMIT   the rest from the slot's stored result: certificate, first
+//             contact and multiccd -- from multiccd_x's stored results when it
+//             ran (xran), else multiccd_q<8> as for a pair on its own
+#define CX_ALL 0
+#define CX_FIRST 1
+#define CX_EMIT 2
+DEVI void collide_convex_mj(const Mdl& md, Dat& d, int pairA, int pairB, int mccd, int xmode = CX_ALL,
+                            int xslot = 0, int xran = 0) {
   const int lane = lane_id();
   const int32_t *p1 = IA(md, pair_geom1), *p2 = IA(md, pair_geom2);
   const int32_t *ghull = IA(md, geom_hullid), *hnum = IA(md, hull_vertnum);
@@ -3333,8 +3531,10 @@ DEVI void collide_convex_mj(const Mdl& md, Dat& d, int pairA, int pairB, int mcc
     const int g1 = lane < 32 ? gA1 : gB1, g2 = lane < 32 ? gA2 : gB2;
     double n[3], depth, pos[3], cd[3], cm;
     const int hit = ccd_mpr(md, d, q, g1, g2, n, &depth, pos, cd, &cm);
-    if ((lane & 31) == 0) mccd_store(d, MCCD_RES2 + 12 * (lane >> 5), hit, n, pos, cd, depth, cm);
+    const int at = xmode == CX_FIRST ? MCCD_XRES1 + 12 * xslot : MCCD_RES2;
+    if ((lane & 31) == 0) mccd_store(d, at + 12 * (lane >> 5), hit, n, pos, cd, depth, cm);
     wsync();
+    if (xmode == CX_FIRST) return;
   }
   const int np = pairB >= 0 ? 2 : 1;
   const double* cp = (const double*)d.poly;
@@ -3346,7 +3546,7 @@ DEVI void collide_convex_mj(const Mdl& md, Dat& d, int pairA, int pairB, int mcc
     int nc = 0;
 #pragma unroll 1
     for (int it = 0; it < 5; it++) {
-      if (it > 0 || pairB < 0) {
+      if (it > 0 || (pairB < 0 && xmode != CX_EMIT)) {
         PairCtx pc;
         if (it > 0) {
           mccd_perturb(d, d, G1, G2, cp + MCCD_N, cp, it - 1, MCCD_POSE);
@@ -3358,10 +3558,13 @@ DEVI void collide_convex_mj(const Mdl& md, Dat& d, int pairA, int pairB, int mcc
         double n[3], depth, pos[3], cd[3], cm;
         const int hit = ccd_mpr(md, d, pc, G1, G2, n, &depth, pos, cd, &cm);
         wsync();
-        if (lane == 0) mccd_store(d, MCCD_RES, hit, n, pos, cd, depth, cm);
+        if (lane == 0) mccd_store(d, xmode == CX_FIRST ? MCCD_XRES1 + 12 * xslot : MCCD_RES, hit, n, pos, cd, depth, cm);
         wsync();
+        if (xmode == CX_FIRST) break;
       }
-      const double* r = it == 0 && pairB >= 0 ? cp + MCCD_RES2 + 12 * k : cp + MCCD_RES;
+      const double* r = it == 0 && xmode == CX_EMIT ? cp + MCCD_XRES1 + 12 * xslot
+                        : it == 0 && pairB >= 0     ? cp + MCCD_RES2 + 12 * k
+                                                    : cp + MCCD_RES;
       const int hk = r[11] != 0.0;
       if (it == 0) {
         PT(4);
@@ -3376,6 +3579,14 @@ DEVI void collide_convex_mj(const Mdl& md, Dat& d, int pairA, int pairB, int mcc
         if (!multi) break;
         const int nm1 = hnum[ghull[G1]], nm2 = hnum[ghull[G2]];
         const bool cyl = cy[2 * G1] > 0.0 || cy[2 * G2] > 0.0;
+        if (xmode == CX_EMIT && xran) {
+          // multiccd_x's four results of this pair, as multiccd_q takes its own
+          double p0[3] = {r[3], r[4], r[5]};
+          mccd_list_init(d, p0);
+          nc = 1;
+          mccd_take_groups(md, d, pair, G1, G2, 4, nc, MCCD_XRES + 48 * xslot);
+          break;
+        }
         if (MGS_MCCD_Q && !cyl && nm1 <= 8 && nm2 <= 8) {
           double n0[3] = {r[0], r[1], r[2]}, p0[3] = {r[3], r[4], r[5]};
           multiccd_q<8>(md, d, pair, G1, G2, n0, p0);
@@ -3828,35 +4039,69 @@ DEVI void collision(const Mdl& md, Dat& d, int mccd = 1) {
     }
     PT(59);
     // convex pairs whose four hulls fit 16-lane rows may go two at a time
-    int small2 = 0;
+    int small2 = 0, xel = 0;
     const int pk = p < npair ? IA(md, pair_kind)[p] : MGS_PAIR_BOXBOX;
     const bool mpr_pair = md.m.ccd_mode == MGS_CCD_R5 ? pk != MGS_PAIR_BOXBOX
                                                        : (pk == MGS_PAIR_CONVEX || pk == MGS_PAIR_CONVEX_SMOOTH);
     if (ov && mpr_pair) {
       const int32_t *ghull = IA(md, geom_hullid), *hnum = IA(md, hull_vertnum);
-      small2 = hnum[ghull[g[0]]] <= 16 && hnum[ghull[g[1]]] <= 16;
+      const int n1 = hnum[ghull[g[0]]], n2 = hnum[ghull[g[1]]];
+      small2 = n1 <= 16 && n2 <= 16;
+      // multiccd_q<8>'s pairs: their multiccd may go several pairs at a time (multiccd_x)
+      const double* cy = DA(md, geom_cyl);
+      xel = MGS_MCCD_X && MGS_MCCD_Q && mccd && md.m.ccd_mode == MGS_CCD_MULTI && pk == MGS_PAIR_CONVEX &&
+            n1 <= 8 && n2 <= 8 && !(cy[2 * g[0]] > 0.0 || cy[2 * g[1]] > 0.0);
     }
     const unsigned long long smallm = __ballot(small2);
+    unsigned long long xelm = __ballot(xel);
     unsigned long long mask = __ballot(ov);
     mask &= ~obb_separated_wave(d, mask, g[0], g[1], D, h[0], h[1], mp);
     PT(60);
     mask &= ~cert_check(md, d, c0, mask);
     PT(3);
+    // multiccd_x rounds: when the loop reaches a pair of xelm that has no slot
+    // yet, the next up to four such pairs (xall, slot = rank of the bit) first
+    // run their first MPRs (xq: those still to run, two at a time) and then
+    // their perturbed MPRs in one call; each then emits from its slot when its
+    // turn comes, so the contacts keep the pair order.  A round of one pair is
+    // left to the path of a pair on its own.
+    unsigned long long xall = 0ull, xq = 0ull;
+    int xran = 0;
     while (mask) {
-      int b = __ffsll((long long)mask) - 1;
-      mask &= mask - 1ull;
-      const int kind = IA(md, pair_kind)[c0 + b];
-      if (((smallm >> b) & 1ull) && mask && ((smallm >> (__ffsll((long long)mask) - 1)) & 1ull)) {
-        int b2 = __ffsll((long long)mask) - 1;
+      int b = __ffsll((long long)mask) - 1, b2 = -1, xmode = CX_ALL, xslot = 0;
+      if (xq) {
+        b = __ffsll((long long)xq) - 1;
+        xq &= xq - 1ull;
+        if (xq) { b2 = __ffsll((long long)xq) - 1; xq &= xq - 1ull; }
+        xmode = CX_FIRST;
+      } else if (((xelm & ~xall) >> b) & 1ull) {
+        unsigned long long t = xelm & mask;
+        xall = 0ull;
+        for (int s = 0; s < 4 && t; s++) { xall |= t & (0ull - t); t &= t - 1ull; }
+        if (xall & (xall - 1ull)) { xq = xall; continue; }
+        xelm &= ~xall;
+        xall = 0ull;
+      }
+      if (xmode != CX_FIRST) {
         mask &= mask - 1ull;
-        if (md.m.ccd_mode == MGS_CCD_R5) collide_pair2(md, d, c0 + b, c0 + b2);
-        else collide_convex_mj(md, d, c0 + b, c0 + b2, mccd);
+        if ((xall >> b) & 1ull) {
+          xmode = CX_EMIT;
+        } else if (((smallm >> b) & 1ull) && mask && ((smallm & ~xall) >> (__ffsll((long long)mask) - 1)) & 1ull) {
+          b2 = __ffsll((long long)mask) - 1;
+          mask &= mask - 1ull;
+        }
+      }
+      if (xmode != CX_ALL) xslot = __popcll(xall & ((1ull << b) - 1ull));
+      const int kind = IA(md, pair_kind)[c0 + b];
+      if (md.m.ccd_mode == MGS_CCD_R5 && b2 >= 0) {
+        collide_pair2(md, d, c0 + b, c0 + b2);
       } else if (kind == MGS_PAIR_BOXBOX) {
         collide_boxbox(md, d, c0 + b);
       } else if (md.m.ccd_mode == MGS_CCD_R5) {
         collide_pair(md, d, c0 + b);
       } else if (kind == MGS_PAIR_CONVEX || kind == MGS_PAIR_CONVEX_SMOOTH) {
-        collide_convex_mj(md, d, c0 + b, -1, mccd);
+        collide_convex_mj(md, d, c0 + b, b2 >= 0 ? c0 + b2 : -1, mccd, xmode, xslot, xran);
+        if (xmode == CX_FIRST && !xq) xran = multiccd_x(md, d, c0, xall);
       } else {
         collide_prim(md, d, c0 + b, kind);
       }
