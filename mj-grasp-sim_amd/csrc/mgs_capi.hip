@@ -59,8 +59,9 @@ bool hbm_extra(const mgs_model_desc& m) { return !MGS_PACKED && m.g_rows_hbm; }
 int layout_maxdim(const mgs_model_desc& m);
 size_t hbm_slice_doubles(const mgs_model_desc& m) {
   const int md = layout_maxdim(m);
+  // (... and the copy of M that integrate restores: the kernel's hbm_slice)
   return (size_t)m.nefc_max * m.nv +
-         (hbm_extra(m) ? (size_t)(K_CERT * CERT_W + 9 * m.ncon_max + md * md * m.ncon_max) : 0);
+         (hbm_extra(m) ? (size_t)(K_CERT * CERT_W + 9 * m.ncon_max + md * md * m.ncon_max + m_square_size(m)) : 0);
 }
 
 // the contact dimension the kernels for this model are built for (MGS_MAXDIM)

@@ -4139,8 +4139,15 @@ enum {
 #ifndef MGS_HBM_EXTRA
 #define MGS_HBM_EXTRA 0
 #endif
+// ... and a copy of the unfactored M for integrate (m_copy_slot), so the step
+// computes crb() once.  MGS_M_KEEP 0 recomputes (A/B builds; the slice keeps
+// its size: the host sizes it without knowing the object's switch)
+#ifndef MGS_M_KEEP
+#define MGS_M_KEEP 1
+#endif
 DEVI size_t hbm_slice(int ne, int nv, int nc) {
-  return (size_t)ne * nv + (MGS_HBM_EXTRA ? (size_t)(K_CERT * CERT_W + 9 * nc + BLKSTRIDE * nc) : 0);
+  return (size_t)ne * nv +
+         (MGS_HBM_EXTRA ? (size_t)(K_CERT * CERT_W + 9 * nc + BLKSTRIDE * nc + TRI_SIZE(nv)) : 0);
 }
 struct Lay {
   int o[L_COUNT];
@@ -6442,12 +6449,18 @@ DEVI void solve(const Mdl& md, Dat& d) {
 // M survives the step in the unused tail of the G rows (rows >= nefc are never
 // read), so integrate need not recompute it: the copy sits in the last nv*nv
 // doubles of the G slot, clear of the dynamics-stage views that share U with G,
-// and is valid while the step's rows stay below it.  The wide build (G in HBM)
-// recomputes.
+// and is valid while the step's rows stay below it.  With G in HBM the copy has
+// a region of its own at the end of the candidate's slice (MGS_HBM_EXTRA
+// objects: after the contact blocks, clear of every row); the wide build (G in
+// HBM without the extra regions) recomputes.
 template <int NV>
 DEVI double* m_copy_slot(const Mdl& md, const Dat& d) {
 #ifdef MGS_G_GLOBAL
+#if MGS_HBM_EXTRA && MGS_M_KEEP
+  return d.con_blk + BLKSTRIDE * md.m.ncon_max;
+#else
   return nullptr;
+#endif
 #else
   const int nv = md.m.nv;
   const int tail0 = md.m.nefc_max * GS - TRI_SIZE(NV);
@@ -6513,7 +6526,11 @@ DEVI void integrate(const Mdl& md, Dat& d) {
   // step's rows left it intact, else recomputed; then MI = M - dt*qDeriv
   {
     const double* mc = m_copy_slot<NV>(md, d);
+#if defined(MGS_G_GLOBAL)
+    if (mc) {     // a region of its own: no row reaches it
+#else
     if (mc && uni(d.NEFC) * GS <= (int)(mc - d.G)) {
+#endif
       for (int k = lane; k < TRI_SIZE(NV); k += WAVE) d.M[k] = mc[k];
       wsync();
     } else {
