@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 23
+#define MGS_ABI_VERSION 24
 #define MGS_NSTATS 6
 /* largest dof count: 64 for the libraries' kernels (one dof per lane), 128
    for model-specialised code objects (two dofs per lane, ABI 22) */
@@ -93,6 +93,9 @@ extern "C" {
                                       mj_checkVel / mj_checkAcc, mjMAXVAL): the candidate stops, label 0 */
 #define MGS_FLAG_PAUSED 8          /* reached mgs_schedule.pause_step unfinished: stopped there with a
                                       resume record (fail_step -4), continued by a later launch */
+#define MGS_FLAG_SKIPPED 16        /* not simulated: popped behind the launch's first
+                                      mgs_schedule.enough_stable stable candidates (ABI 24; label 0,
+                                      fail_step MGS_FAIL_SKIPPED, the other stats 0) */
 #define MGS_MAXVAL 1e10
 
 /* fail_step values below -1 (label 0): -2 collision-mask reject (not simulated), -3 stopped at a
@@ -101,6 +104,11 @@ extern "C" {
  * ring (ABI 20).  Its continuation overwrites it, so it survives a launch only if the candidate was
  * lost -- never in a correct run; callers of the device entries treat it as an error. */
 #define MGS_FAIL_YIELDED (-5)
+/* MGS_FAIL_SKIPPED (ABI 24): not simulated, because at least mgs_schedule.enough_stable candidates
+ * with a smaller index had already ended stable in the same launch (the reference stops simulating
+ * there too).  obj_qpos holds the initial object pose, stats[2] = MGS_FLAG_SKIPPED, the resume
+ * record is not touched. */
+#define MGS_FAIL_SKIPPED (-6)
 
 /* narrowphase of a geom pair (pair_kind).  With ccd_mode 0 only the first two
  * occur; with ccd_mode 1 / 2 the pairs follow MuJoCo 3.2.2's collision table
@@ -341,6 +349,24 @@ typedef struct mgs_schedule {
                             than resident workgroups then runs them round robin and ends about
                             one slice after the last one finishes; outputs are those of one
                             uninterrupted run (the record is the complete state).  0 = off */
+  int32_t enough_stable; /* K > 0 (on a work-queue launch): candidates behind the launch's first K
+                            stable ones are not simulated (ABI 24).  The queue hands indices out in
+                            ascending order, so once K candidates have finished with label 1, a
+                            freshly taken index has K stable ones before it: the first-K rule
+                            (apply_enough_stable) reports it False whatever its rollout would
+                            give.  It gets label 0, fail_step MGS_FAIL_SKIPPED, the initial object
+                            pose and stats[2] = MGS_FLAG_SKIPPED; in mgs_mask_rollout_device its
+                            mask is still computed, and a mask or d_active reject keeps the reject
+                            outputs.  Candidates running or yielded when the count reaches K still
+                            run to the end, so more may run than the rule needs, never fewer:
+                            the first-K rule over these labels equals the rule over a full
+                            run's.  Honoured by mgs_rollout, mgs_rollout_resume,
+                            mgs_rollout_device, mgs_rollout_resumable_device and
+                            mgs_mask_rollout_device when they run as a work queue
+                            (mgs_rollout_queue mode >= 1 and more candidates than the grid);
+                            ignored (nothing skipped, nothing counted) in mode 0, by
+                            mgs_rollout_list_device, and by mgs_simulate / mgs_simulate_device,
+                            where every state ends "ok".  0 = off */
 } mgs_schedule;
 
 /* per-candidate rollout outputs */

@@ -223,6 +223,7 @@ struct mgs_batch {
   int qslot;                        // ring head / tail, ring address), one per launch in a ring of
                                     // MGS_QUEUE_RING (launches in flight on other streams keep their
                                     // own); each launch's last workgroup returns its counters to zero
+                                    // (the enough_stable count of ABI 24, word MGS_QSTABLE, included)
   uint32_t* d_rings;                // rotation rings (ABI 19), MGS_QRING_F(ring_n) words per header,
   int ring_n;                       // allocated on the first launch with yield_every > 0 and grown
                                     // when a launch's n exceeds ring_n (the kernel indexes a ring by
@@ -721,6 +722,7 @@ int mgs_simulate_device(mgs_batch* b, const mgs_schedule* sched, int n, const do
   if (!b || !sched || !d_state_out || n < 0 || n > b->cap) return fail(MGS_EINVAL, "mgs_simulate_device: bad argument%s");
   mgs_schedule s = *sched;   // no contact checks: a free simulation never stops early
   for (int p = 0; p < MGS_MAX_PHASES; p++) { s.check_every[p] = 0; s.check_at_end[p] = 0; }
+  s.enough_stable = 0;       // every state ends "ok" here: nothing to count, nothing to skip
   return launch_rollout(b, &s, n, d_qpos_init, d_mocap_quat, d_phase_start, d_phase_target, nullptr, b->d_label,
                         b->d_fail, b->d_objq, d_stats ? d_stats : b->d_stats, d_vstate_init, d_state_out, stream);
 }

@@ -6759,7 +6759,11 @@ DEVI void save_record(const Mdl& md, Dat& d, double* rec, int p, int t, int gste
 // launched, so a ring slot index never leaves its allocation).  [8..9] /
 // [10..11]: the launch's start / end on the 100 MHz real-time counter (the
 // workgroup that takes candidate 0 / the last one to leave; mgs_queue_spans).
-#define MGS_QHDR 12
+// [12] the launch's finished stable candidates (ABI 24, mgs_schedule.
+// enough_stable; the last workgroup out zeroes it with words 0, 2 and 3),
+// [13] padding (the 64-bit words of every header stay 8-byte aligned).
+#define MGS_QHDR 14
+#define MGS_QSTABLE 12
 #define MGS_QRING_F(n) (2u * (uint32_t)(n))
 #ifndef MGS_SPIN_MAX
 #define MGS_SPIN_MAX (1u << 22)
@@ -6834,17 +6838,18 @@ DEVI int ring_pop(uint32_t* q, int n) {
   return c;
 }
 
-// one candidate's rollout (the body of mgs_rollout_kernel)
+// one candidate's rollout (the body of mgs_rollout_kernel); returns 1 if the
+// candidate ended here with label 1 (not rejected, skipped, yielded or stopped)
 template <int NV, int SL>
-DEVI void rollout_one(const Mdl& md, double* smem, const Lay& lay, const mgs_schedule& sc, int i,
-                      const double* __restrict__ qpos_init, const double* __restrict__ mocap_quat,
-                      const double* __restrict__ phase_start, const double* __restrict__ phase_target,
-                      const uint8_t* __restrict__ active, uint8_t* __restrict__ label,
-                      int32_t* __restrict__ fail_step, double* __restrict__ obj_qpos, int32_t* __restrict__ stats,
-                      const double* __restrict__ vstate_init, double* __restrict__ state_out,
-                      double* resume_out, const double* resume_in, const double* __restrict__ mask_mpos,
-                      int mask_pred, uint8_t* __restrict__ mask_out, int32_t* ovf_count, int32_t* ovf_list,
-                      uint32_t* yq = nullptr, int n = 0, int from_ring = 0) {
+DEVI int rollout_one(const Mdl& md, double* smem, const Lay& lay, const mgs_schedule& sc, int i,
+                     const double* __restrict__ qpos_init, const double* __restrict__ mocap_quat,
+                     const double* __restrict__ phase_start, const double* __restrict__ phase_target,
+                     const uint8_t* __restrict__ active, uint8_t* __restrict__ label,
+                     int32_t* __restrict__ fail_step, double* __restrict__ obj_qpos, int32_t* __restrict__ stats,
+                     const double* __restrict__ vstate_init, double* __restrict__ state_out,
+                     double* resume_out, const double* resume_in, const double* __restrict__ mask_mpos,
+                     int mask_pred, uint8_t* __restrict__ mask_out, int32_t* ovf_count, int32_t* ovf_list,
+                     uint32_t* yq = nullptr, int n = 0, int from_ring = 0, int skip = 0) {
   int lane = lane_id();
   if (from_ring) {
     // a candidate that yielded earlier in this launch: accepted, and its
@@ -6868,18 +6873,22 @@ DEVI void rollout_one(const Mdl& md, double* smem, const Lay& lay, const mgs_sch
     wsync();
     reject = hit;
   }
-  if (reject) {
-    // collision-mask reject: not simulated (filter_to_stable.py:39-44)
+  if (reject || skip) {
+    // not simulated: a collision-mask reject (filter_to_stable.py:39-44), else
+    // a candidate behind the launch's first enough_stable stable ones (ABI 24:
+    // the first-K rule reports it False whatever its rollout would give,
+    // mgs/env/gravityless_object_grasping.py:151-156)
+    const int sk = !reject;
     if (lane == 0) {
       label[i] = 0;
-      if (fail_step) fail_step[i] = -2;
+      if (fail_step) fail_step[i] = sk ? MGS_FAIL_SKIPPED : -2;
       if (stats)
-        for (int k = 0; k < MGS_NSTATS; k++) stats[MGS_NSTATS * i + k] = 0;
+        for (int k = 0; k < MGS_NSTATS; k++) stats[MGS_NSTATS * i + k] = (sk && k == 2) ? MGS_FLAG_SKIPPED : 0;
     }
     // no object joint reported (obj_qposadr < 0): zeros, as the oracle's output
     if (obj_qpos && lane < 7)
       obj_qpos[7 * i + lane] = sc.obj_qposadr >= 0 ? qpos_init[(size_t)i * md.m.nq + sc.obj_qposadr + lane] : 0.0;
-    return;
+    return 0;
   }
   Dat d;
   bind<SL>(d, smem, lay);
@@ -7042,7 +7051,7 @@ DEVI void rollout_one(const Mdl& md, double* smem, const Lay& lay, const mgs_sch
   }
   if (fstep == -5) {   // yielded: another workgroup of this launch continues it
     PROF_FLUSH
-    return;
+    return 0;
   }
   if (lane == 0) {
     label[i] = (uint8_t)ok;
@@ -7065,6 +7074,7 @@ DEVI void rollout_one(const Mdl& md, double* smem, const Lay& lay, const mgs_sch
     for (int k = lane; k < md.m.nact; k += WAVE) so[nq + 2 * nv + k] = d.act[k];
   }
   PROF_FLUSH
+  return ok;
 }
 
 // One workgroup (one wave) per candidate: candidate blockIdx.x, or -- list mode
@@ -7107,15 +7117,30 @@ DEVI void rollout_entry(double* smem, const Mdl& mdarg, const int32_t* __restric
     // first, then the ring of yielded ones; a workgroup leaves when both are
     // empty (a candidate pushed later is taken by its pusher's own next pop)
     uint32_t* yq = (sc.yield_every > 0 && resume_out && ring_of(queue)) ? queue : nullptr;
+    // enough_stable (ABI 24): fresh indices are popped in ascending order, so
+    // every finished candidate has a smaller index than one popped later; once
+    // the launch's count of finished stable candidates has reached K, a freshly
+    // popped candidate has K stable ones before it and is not simulated (its
+    // mask, in the fused launch, still is).  The count is read (acquire) just
+    // before the pop and a finished candidate adds to it with release, so each
+    // counted candidate's own pop is ordered before this one, however long a
+    // wave waits between the two instructions.  The count misses candidates
+    // that are running, yielded or stopped: the skip is conservative, never
+    // wrong.  Ring pops are never skipped (they were popped fresh earlier)
     int fresh = 1;
     for (;;) {
-      int s = -1, ring = 0;
+      int s = -1, ring = 0, skip = 0;
       if (fresh) {
         uint32_t t = 0;
+        if (sc.enough_stable > 0) {
+          uint32_t c = 0;
+          if (lane_id() == 0) c = __hip_atomic_load(queue + MGS_QSTABLE, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+          skip = __builtin_amdgcn_readfirstlane(c) >= (uint32_t)sc.enough_stable;
+        }
         if (lane_id() == 0) t = __hip_atomic_fetch_add(queue, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const uint32_t u = __builtin_amdgcn_readfirstlane(t);
         if (u < (uint32_t)n) s = (int)u;
-        else fresh = 0;
+        else fresh = skip = 0;
         if (u == 0 && lane_id() == 0)
           __hip_atomic_store((unsigned long long*)(queue + 8), (unsigned long long)__builtin_amdgcn_s_memrealtime(),
                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -7125,9 +7150,14 @@ DEVI void rollout_entry(double* smem, const Mdl& mdarg, const int32_t* __restric
         ring = 1;
       }
       if (s < 0) break;
-      rollout_one<NV, SL>(md, smem, lay, sc, s, qpos_init, mocap_quat, phase_start, phase_target, active, label,
-                          fail_step, obj_qpos, stats, vstate_init, state_out, resume_out, resume_in, mask_mpos,
-                          mask_pred, mask_out, ovf_count, ovf_list, yq, n, ring);
+      const int ok = rollout_one<NV, SL>(md, smem, lay, sc, s, qpos_init, mocap_quat, phase_start, phase_target,
+                                         active, label, fail_step, obj_qpos, stats, vstate_init, state_out,
+                                         resume_out, resume_in, mask_mpos, mask_pred, mask_out, ovf_count, ovf_list,
+                                         yq, n, ring, skip);
+      // a finished stable candidate, after lane 0's label store: an index popped
+      // after a load that saw this add has this candidate before it
+      if (sc.enough_stable > 0 && ok && lane_id() == 0)
+        __hip_atomic_fetch_add(queue + MGS_QSTABLE, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (lane_id() == 0 &&
         __hip_atomic_fetch_add(queue + 1, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
@@ -7136,6 +7166,7 @@ DEVI void rollout_entry(double* smem, const Mdl& mdarg, const int32_t* __restric
       __hip_atomic_store(queue, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(queue + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(queue + 3, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(queue + MGS_QSTABLE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(queue + 1, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
     return;

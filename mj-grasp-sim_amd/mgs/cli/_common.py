@@ -30,11 +30,19 @@ def save_grasps(path, poses, joints):
     np.savez(path, **{"pose": poses.to_mat(), "joints": joints})
 
 
-def evaluators(env, cfg):
+def evaluators(env, cfg, enough_stable=None):
     """(collision_mask, stable_mask) callables on (poses, joints) of a
     GravitylessObjectGrasping env for this configuration's horizon -- the two
-    stages the CLIs shard over ranks (mgs.env.sharding)."""
+    stages the CLIs shard over ranks (mgs.env.sharding).  enough_stable = K
+    (default: the configuration's `enough_stable`, if it has one): the
+    stability stage skips the rollouts behind its first K stable grasps (a
+    rank's own first K hold its share of the global first K, so the global
+    rule applied after the gather is unchanged)."""
     kw = horizon_kwargs(cfg)
+    if enough_stable is None:
+        enough_stable = cfg.get("enough_stable")
+    if enough_stable is not None:
+        kw["enough_stable"] = int(enough_stable)
     return env.grasp_collision_mask, lambda p, j: env.grasp_stability_evaluation_from_joints(p, j, **kw)
 
 

@@ -24,7 +24,10 @@ def run(cfg):
     env = GravitylessObjectGrasping(get_gripper(cfg.gripper), get_object(oid), device=cli_device())
     d = grasp_dir(cfg, oid, "MGS_INPUT_DIR")
     poses, joints = load_grasps(os.path.join(d, "candidates.npz"))
-    mask, mm = filter_sharded(*_common.evaluators(env, cfg), poses, joints, enough_stable=1000)
+    # the reference's K (filter_to_stable.py:47), carried by the configuration so
+    # that the stability stage skips the rollouts behind it (_common.evaluators)
+    es = cfg.setdefault("enough_stable", 1000)
+    mask, mm = filter_sharded(*_common.evaluators(env, cfg), poses, joints, enough_stable=es)
     poses_cf, joints_cf = poses[mask], joints[mask]
     if rank == 0:
         print(sum(mask))

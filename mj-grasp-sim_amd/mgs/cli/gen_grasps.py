@@ -41,7 +41,7 @@ def run(cfg):
     t1 = time.perf_counter()
     env = GravitylessObjectGrasping(gripper, obj, device=cli_device())
     poses = SE3Pose.from_mat(H, type="wxyz")
-    es = cfg.get("enough_stable", 1000)
+    es = cfg.setdefault("enough_stable", 1000)     # _common.evaluators reads it: the stability stage skips behind it
     mask, mm = filter_sharded(*_common.evaluators(env, cfg), poses, J, enough_stable=es)
     pc, jc = poses[mask], J[mask]
     t2 = time.perf_counter()

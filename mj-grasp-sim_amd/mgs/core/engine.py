@@ -338,7 +338,8 @@ class Engine:
         """doubles per resume record (mgs_rollout_out.resume)"""
         return self.cm.nq + 2 * self.cm.nv + int(self.cm.nact) + abi.MGS["MGS_RESUME_EXTRA"]
 
-    def rollout(self, plan, resumable=False, resume_from=None, pause_step=0, capped_continue=False, yield_every=0):
+    def rollout(self, plan, resumable=False, resume_from=None, pause_step=0, capped_continue=False, yield_every=0,
+                enough_stable=0):
         """mgs_rollout.  resumable: candidates overflowing the capacity stop at
         that step (fail_step -3) and result["resume"] holds their records;
         resume_from: records of such a capped run, continued here
@@ -348,13 +349,18 @@ class Engine:
         slice a later call continues; capped_continue: over-capacity candidates
         run on capped and flagged instead of stopping.  yield_every > 0 (needs
         resumable): in-launch rotation (mgs_schedule.yield_every) when the batch
-        has more rollouts than the resident grid; outputs are unchanged."""
+        has more rollouts than the resident grid; outputs are unchanged.
+        enough_stable = K > 0 (mgs_schedule.enough_stable): on a work-queue
+        launch, candidates taken after K earlier ones of this call ended stable
+        are not simulated (label 0, fail_step MGS_FAIL_SKIPPED, stats[2] =
+        MGS_FLAG_SKIPPED); the first-K rule over the labels is unchanged."""
         n = len(plan.qpos_init)
         sched = abi.make_schedule(plan.nsteps, plan.check_every, plan.check_at_end, plan.ctrl, plan.obj_qposadr,
                                   check_offset=getattr(plan, "check_offset", None))
         sched.pause_step = int(pause_step)
         sched.capped_continue = int(bool(capped_continue))
         sched.yield_every = int(yield_every)
+        sched.enough_stable = max(0, int(enough_stable))
         if yield_every and not resumable:
             raise ValueError("yield_every needs resumable=True (a yielded state goes to the resume records)")
         if pause_step and not resumable:

@@ -33,7 +33,8 @@ import numpy as np
 
 from mgs.core.abi import MGS
 from mgs.core.mjcf import CompiledModel, compile_xml
-from mgs.env.gravityless_object_grasping import RolloutPlan, apply_enough_stable, sliced_rollout
+from mgs.env.gravityless_object_grasping import (GravitylessObjectGrasping, RolloutPlan, apply_enough_stable,
+                                                 sliced_rollout)
 from mgs.util.geo.transforms import SE3Pose
 
 # stats[:, 2] flags that a wider re-run resolves (contacts / rows over capacity);
@@ -388,19 +389,25 @@ class ClutterTableEnv:
     # in-launch rotation and explicit relaunch slices, as GravitylessObjectGrasping
     YIELD_EVERY = 32
     SLICES = 1
+    # device skip of the rollouts behind the first enough_stable stable grasps
+    # (mgs_schedule.enough_stable), as GravitylessObjectGrasping.WORK_SKIP
+    WORK_SKIP = True
+    SKIP_YIELD_EVERY = 0
+    skip_setting = GravitylessObjectGrasping.skip_setting
 
     def rollout(self, plan: RolloutPlan, env_state, max_ncon: int = 128, slices: Optional[int] = None,
-                yield_every: Optional[int] = None, on_capacity: str = "raise"):
+                yield_every: Optional[int] = None, on_capacity: str = "raise", enough_stable=None):
         """engine rollout with contact-capacity escalation (continued from the
         overflowing step), in-launch rotation and optional time slices by
         relaunch, as GravitylessObjectGrasping.rollout (sliced_rollout; a
         candidate still over max_ncon raises CapacityError unless
-        on_capacity="capped")."""
+        on_capacity="capped").  enough_stable = K: candidates behind the first
+        K stable ones are not simulated (WORK_SKIP; res['skipped'])."""
+        K, yield_every = self.skip_setting(len(plan.qpos_init), enough_stable, yield_every)
         return sliced_rollout(plan, self.engine_for_state(env_state),
                               lambda c: self.engine_for_state(env_state, ncon_max=c), self.ncon_max, max_ncon,
                               self.SLICES if slices is None else slices,
-                              yield_every=self.YIELD_EVERY if yield_every is None else yield_every,
-                              on_capacity=on_capacity)
+                              yield_every=yield_every, on_capacity=on_capacity, enough_stable=K)
 
     def grasp_stable_mask(self, poses: SE3Pose, joints: np.ndarray, env_state, nstep_lift: int = 3000,
                           lift_dist: float = 0.3, enough_stable=None, *, close_steps: Optional[int] = None,
@@ -410,7 +417,7 @@ class ClutterTableEnv:
         if len(poses) == 0:
             return np.zeros(0, dtype=bool)
         plan = self.stable_plan(poses, joints, env_state, nstep_lift, lift_dist, close_steps)
-        res = self.rollout(plan, env_state)
+        res = self.rollout(plan, env_state, enough_stable=enough_stable)
         labels = apply_enough_stable(res["label"].astype(bool), enough_stable)
         if return_details:
             res["label"] = labels

@@ -208,17 +208,37 @@ class GravitylessObjectGrasping:
     # library's rows), as ClutterTableEnv; MuJoCo has no cap, so a candidate
     # still over it fails the call (sliced_rollout, on_capacity="raise")
     MAX_NCON = 128
+    # rollouts behind the first enough_stable stable grasps are skipped on the
+    # device (mgs_schedule.enough_stable); False: every collision-free candidate
+    # is simulated and the first-K rule applied afterwards only (A/B runs, tests)
+    WORK_SKIP = True
+    # rotation of a call that can skip (enough_stable below its candidate count,
+    # no explicit yield_every): off.  Rotation starts every candidate of a launch
+    # within a few slices, before any has finished, and only un-started
+    # candidates can be skipped; without it the launch's tail is the candidates
+    # in flight when the count reaches K, which is what rotation was for
+    SKIP_YIELD_EVERY = 0
+
+    def skip_setting(self, n, enough_stable, yield_every):
+        """(enough_stable, yield_every) of a rollout call over n candidates"""
+        K = enough_stable if self.WORK_SKIP else None
+        if yield_every is None:
+            can_skip = K is not None and 0 < int(K) < n
+            yield_every = self.SKIP_YIELD_EVERY if can_skip else self.YIELD_EVERY
+        return K, yield_every
 
     def rollout(self, plan: "RolloutPlan", max_ncon: Optional[int] = None, slices: Optional[int] = None,
-                yield_every: Optional[int] = None, on_capacity: str = "raise"):
+                yield_every: Optional[int] = None, on_capacity: str = "raise", enough_stable=None):
         """engine.rollout with capacity escalation, in-launch rotation and
         optional time slices by relaunch (sliced_rollout below), on the engine
-        that finishes a call of this size first (engine_for_rollouts)."""
+        that finishes a call of this size first (engine_for_rollouts).
+        enough_stable = K: candidates behind the first K stable ones are not
+        simulated (WORK_SKIP; res['skipped'])."""
+        K, yield_every = self.skip_setting(len(plan.qpos_init), enough_stable, yield_every)
         return sliced_rollout(plan, self.engine_for_rollouts(len(plan.qpos_init)), self.engine_for, self.ncon_max,
                               self.MAX_NCON if max_ncon is None else max_ncon,
                               self.SLICES if slices is None else slices,
-                              yield_every=self.YIELD_EVERY if yield_every is None else yield_every,
-                              on_capacity=on_capacity)
+                              yield_every=yield_every, on_capacity=on_capacity, enough_stable=K)
 
     # -- host-side bookkeeping (exactly the reference's arithmetic) ------------
     def _check_inputs(self, poses, joints, check_width=True):
@@ -307,7 +327,7 @@ class GravitylessObjectGrasping:
             return np.zeros(0, dtype=bool)
         plan = self.rollout_plan(poses, joints, nstep_lift, lift_dist, shake_steps, shake_dist,
                                  close_steps=close_steps, lift_check_every=lift_check_every)
-        res = self.rollout(plan)
+        res = self.rollout(plan, enough_stable=enough_stable)
         labels = apply_enough_stable(res["label"].astype(bool), enough_stable)
         if return_details:
             res["label"] = labels
@@ -354,7 +374,7 @@ class CapacityError(RuntimeError):
 
 
 def sliced_rollout(plan: "RolloutPlan", engine, engine_for, cap: int, max_ncon: int, slices: int = 1,
-                   yield_every: int = 0, on_capacity: str = "raise"):
+                   yield_every: int = 0, on_capacity: str = "raise", enough_stable=None):
     """A batch's rollouts on `engine` (capacity `cap` contacts) with capacity
     escalation and time slices; results equal one launch at unlimited capacity.
 
@@ -378,7 +398,18 @@ def sliced_rollout(plan: "RolloutPlan", engine, engine_for, cap: int, max_ncon: 
     survivors (one host round trip per slice; profiles/r04b_api.txt).
 
     Records carry the complete state, so either way the results equal one
-    uninterrupted launch's bit for bit."""
+    uninterrupted launch's bit for bit.
+
+    enough_stable = K (None: off): candidates behind the first K stable ones are
+    not simulated (mgs_schedule.enough_stable: label False, fail_step
+    MGS_FAIL_SKIPPED, the initial object pose, stats[2] = MGS_FLAG_SKIPPED;
+    res['skipped'] counts them).  A label of True is final in this flow, so after
+    every launch the host knows, for each candidate i, how many final stable
+    labels precede it; a candidate with K or more is dropped from the next
+    escalation stage or slice (and never raises CapacityError), and a launch on
+    the ascending subset `sub` gets K minus the count before sub[0].  More may
+    run than the first-K rule needs, never fewer: apply_enough_stable over the
+    returned labels equals apply_enough_stable over a full run's."""
     if on_capacity not in ("raise", "capped"):
         raise ValueError(f"on_capacity must be 'raise' or 'capped', not {on_capacity!r}")
     n = len(plan.qpos_init)
@@ -387,14 +418,38 @@ def sliced_rollout(plan: "RolloutPlan", engine, engine_for, cap: int, max_ncon: 
     bounds = [int(round(H * (j + 1) / slices)) for j in range(slices - 1)] + [0]
     capped_ok = on_capacity == "capped"
     last_cap = cap >= max_ncon and capped_ok
+    K = int(enough_stable) if enough_stable is not None and int(enough_stable) > 0 else None
+
+    def behind(sub):
+        """sub without the candidates that have K final stable labels before
+        them (marked skipped as the kernel marks its own), and the keyword of a
+        launch over the rest"""
+        if K is None or not len(sub):
+            return sub, {}
+        lab = res["label"].astype(np.int64)
+        before = np.cumsum(lab) - lab
+        drop = sub[before[sub] >= K]
+        if len(drop):
+            a = plan.obj_qposadr
+            res["label"][drop] = False
+            res["fail_step"][drop] = MGS["MGS_FAIL_SKIPPED"]
+            res["obj_qpos"][drop] = plan.qpos_init[drop, a:a + 7] if a >= 0 else 0.0
+            res["stats"][drop] = 0
+            res["stats"][drop, 2] = MGS["MGS_FLAG_SKIPPED"]
+            sub = sub[before[sub] < K]
+        return sub, (dict(enough_stable=K - int(before[sub[0]])) if len(sub) else {})
+
     res = engine.rollout(plan, resumable=True, pause_step=bounds[0], capped_continue=last_cap,
-                         yield_every=yield_every)
+                         yield_every=yield_every, **({} if K is None else dict(enough_stable=K)))
     rec = res.pop("resume")
     live = np.arange(n)
     for j, b in enumerate(bounds):
         if j > 0:
+            live, kw = behind(live)
+            if not len(live):
+                break
             sub = engine.rollout(plan.subset(live), resumable=True, resume_from=rec[live], pause_step=b,
-                                 capped_continue=last_cap, yield_every=yield_every)
+                                 capped_continue=last_cap, yield_every=yield_every, **kw)
             for k in ("label", "fail_step", "obj_qpos", "stats"):
                 res[k][live] = sub[k]
             rec[live] = sub["resume"]
@@ -402,19 +457,24 @@ def sliced_rollout(plan: "RolloutPlan", engine, engine_for, cap: int, max_ncon: 
         ov = live[(flags & FLAG_CAPACITY) != 0] if not last_cap else live[:0]
         c = cap
         while len(ov) and c < max_ncon:
+            ov, kw = behind(ov)
+            if not len(ov):
+                break
             c = min(2 * c, max_ncon)
             last = c >= max_ncon and capped_ok
             sub = engine_for(c).rollout(plan.subset(ov), resumable=True, resume_from=rec[ov], capped_continue=last,
-                                        yield_every=yield_every)
+                                        yield_every=yield_every, **kw)
             for k in ("label", "fail_step", "obj_qpos", "stats"):
                 res[k][ov] = sub[k]
             keep = np.nonzero(sub["stats"][:, 2] & FLAG_CAPACITY)[0] if not last else np.zeros(0, np.int64)
             rec[ov[keep]] = sub["resume"][keep]
             ov = ov[keep]
+        ov, _ = behind(ov)       # the reference never simulates these: no capacity error for them
         if len(ov) and not capped_ok:
             raise CapacityError(ov, max_ncon)
         live = live[(flags & MGS["MGS_FLAG_PAUSED"]) != 0]
         if not len(live):
             break
     res["overflow"] = int(((res["stats"][:, 2] & FLAG_CAPACITY) != 0).sum()) if n else 0
+    res["skipped"] = int(((res["stats"][:, 2] & MGS["MGS_FLAG_SKIPPED"]) != 0).sum()) if n else 0
     return res
