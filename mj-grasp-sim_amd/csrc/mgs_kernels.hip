@@ -39,10 +39,10 @@
 #define CERT_STORE 1e-6
 #define CERT_EPS 1e-10
 #define WAVE 64
-// row stride of the constraint matrix G (doubles).  An odd stride (NV + 1) makes
-// row walks bank-conflict free but measured no faster and costs 680 B of LDS
-// G row stride (doubles): NV + MGS_GPAD.  With lanes over rows reading G[r * GS + k],
-// an odd stride spreads the 32 lanes of a ds_read_b64 group over distinct banks
+// row stride of the constraint matrix G (doubles): NV + MGS_GPAD.  With lanes
+// over rows reading G[r * GS + k], an odd stride spreads the 32 lanes of a
+// ds_read_b64 group over distinct banks (pad 1, the default with G in LDS, at
+// the even dof counts of the shipped models).  G rows in HBM are unpadded
 #ifndef MGS_GPAD
 #ifdef MGS_G_GLOBAL
 #define MGS_GPAD 0
@@ -2495,11 +2495,6 @@ DEVI void collide_boxbox(const Mdl& md, Dat& d, int pair) {
 // Primitive pairs: the analytic colliders.  Parity vs MuJoCo unpinned
 // (DESIGN.md §2); GPU == oracle bit for bit.
 #define CCD_EPS 2.2204460492503131e-16
-// multiccd's four perturbations on 16-lane groups at once (1, ccd_mpr_q) or
-// one after another on the whole wave (0: A/B builds)
-#ifndef MGS_MCCD_Q
-#define MGS_MCCD_Q 1
-#endif
 #define MCCD_RELTOL 1e-3
 #define MCCD_C 0.9999998750000026       // cos(5e-4): half the perturbation angle
 #define MCCD_S 4.999999791666669e-04    // sin(5e-4)
@@ -2719,8 +2714,8 @@ DEVI int ccd_mpr(const Mdl& md, const Dat& d, const Ctx& pc, int g1, int g2, dou
 // first contact (n, pos) is in; four more MPRs with geom 1 turned by -+angle
 // and geom 2 by the opposite angle about the frame's tangents, each new
 // contact farther than MCCD_RELTOL x the smaller bounding radius from the
-// pair's contacts so far added (all lanes; lane 0 writes)
-// the pair's contacts so far, for multiccd's distinctness test: in the
+// pair's contacts so far added (all lanes; lane 0 writes).
+// The pair's contacts so far, for multiccd's distinctness test: in the
 // collision stage's polygon scratch (unused by the ccd_mode 1 / 2 colliders),
 // uniform addresses, lane 0 writes (registers here spilled the object)
 DEVI void mccd_list_init(Dat& d, const double* pos) {
@@ -2756,7 +2751,8 @@ DEVI double mccd_tol(const Mdl& md, int g1, int g2) {
 // two hulls have at most HW vertices: HW 8 -> four MPRs per pass, HW 16 ->
 // two.  Each group computes exactly what the whole wave computes for its
 // perturbation (the MPR's control flow depends only on values uniform within
-// a group), so the contacts are multiccd()'s, bit for bit.
+// a group), so the contacts are those of the oracle's perturbation loop in
+// collide_convex_mj (oracle/mgs_oracle.c), bit for bit.
 template <int HW>
 struct PairCtxQ {
   int n;               // this lane's hull: its vertex count,
@@ -2993,18 +2989,24 @@ DEVI int ccd_mpr_q(const Mdl& md, const Dat& d, const QC& pc, double* n, double*
   return hit;
 }
 
-// scratch after the perturbed poses: the first contact's normal (MCCD_N), an
-// MPR's results (MCCD_RES + 12 k: n pos dir depth cm hit; k the group of
-// multiccd_q) and the two-pair MPR's per pair (MCCD_RES2 + 12 k: they must
-// outlive pair A's multiccd)
-#define MCCD_N 40
+// The collision stage's polygon scratch in the ccd_mode 1 / 2 colliders
+// (doubles; K_POLY_POINTS * 3 = 552):
+//   0 .. 14                a pair's contacts so far (mccd_list_*, at most five)
+//   MCCD_RES + 12 k        an MPR's results: n pos dir depth cm hit; the single
+//                          pair's first MPR at k = 0, then k the group of
+//                          multiccd_q / multiccd_w
+//   MCCD_RES2 + 12 k       the two-pair MPR's per pair (they must outlive pair
+//                          A's multiccd)
+//   MCCD_POSEW + 24 q      multiccd_w's four perturbed poses (R1 R2 x1 x2)
+//   MCCD_XRES1 + 12 slot   multiccd_x (below): the first MPRs' results of a
+//                          round's up to four pairs
+//   MCCD_XRES + 12 (4 slot + perturbation)   and their perturbed MPRs'
+// The last two lie past what the colliders that may run between a pair's
+// stages write (collide_boxbox below 144, multiccd_q / the two-pair MPR below
+// 120, multiccd_w's poses below MCCD_POSEW + 96 = 224).
 #define MCCD_RES 48
 #define MCCD_RES2 96
-// multiccd_x (below): the first MPRs' results of a round's up to four pairs
-// (MCCD_XRES1 + 12 slot) and their perturbed MPRs' (MCCD_XRES + 12 (4 slot +
-// perturbation)), past what the colliders that may run between a pair's
-// stages write (collide_boxbox below 144, multiccd_q / the two-pair MPR below
-// 120, multiccd_w's poses below MCCD_POSEW + 96 = 224); K_POLY_POINTS * 3 = 552
+#define MCCD_POSEW 128
 #define MCCD_XRES1 224
 #define MCCD_XRES 272
 static_assert(MCCD_XRES + 16 * 12 <= K_POLY_POINTS * 3, "multiccd_x results past the polygon scratch");
@@ -3040,9 +3042,10 @@ DEVI void mccd_take_groups(const Mdl& md, Dat& d, int pair, int g1, int g2, int 
   }
   wsync();
 }
-// multiccd() with its four perturbed MPRs on groups of 2 x HW lanes (pairs
-// whose hulls have at most HW vertices and no cylinder): the same contacts in
-// the same order
+// the oracle's perturbation loop (collide_convex_mj, oracle/mgs_oracle.c)
+// with its four perturbed MPRs on groups of 2 x HW lanes (pairs whose hulls
+// have at most HW vertices and no cylinder): the same contacts in the same
+// order
 template <int HW>
 DEVI void multiccd_q(const Mdl& md, Dat& d, int pair, int g1, int g2, const double* n, const double* pos) {
   constexpr int G = WAVE / (2 * HW);      // perturbations per pass
@@ -3067,11 +3070,10 @@ DEVI void multiccd_q(const Mdl& md, Dat& d, int pair, int g1, int g2, const doub
   wsync();
 }
 
-// the perturbed poses go to the collision stage's polygon scratch after the
-// contact list (R1 R2 x1 x2 at MCCD_POSE), lane 0 writing: the context is then
-// read back like an unperturbed one (perturbed poses held in registers across
-// the MPR spilled the eight-per-CU object)
-#define MCCD_POSE 16
+// perturbation q of a pair's poses to the collision stage's polygon scratch
+// (R1 R2 x1 x2 at `at`), lane 0 writing: the MPR reads them from there
+// (perturbed poses held in registers across the MPR spilled the eight-per-CU
+// object)
 DEVI void mccd_perturb(const Dat& d, Dat& dw, int g1, int g2, const double* n, const double* pv, int q, int at) {
   const int ax = q >> 1, sg = q & 1;
   double t1[3], t2[3];
@@ -3110,60 +3112,19 @@ DEVI void mccd_perturb(const Dat& d, Dat& dw, int g1, int g2, const double* n, c
 // of more than 8 vertices, or a cylinder: the gripper's link meshes on the
 // object), in lockstep on four 16-lane groups as there (ccd_mpr_q): four MPR
 // scalar chains at once instead of one after another, the same supports, the
-// same contacts in the same order.  PairCtxW (MGS_MCCD_G 0): each support of
-// the four perturbations computed by the whole wave in turn (support_pair over
-// the pair's hulls, the group's perturbed poses from LDS, only for the groups
-// still running); PairCtxG below (the default): by the group itself
-#ifndef MGS_MCCD_W
-#define MGS_MCCD_W 1   // 0: these perturbations one after another (A/B builds)
-#endif
-#define MCCD_POSEW 128   // the four perturbed poses (24 doubles each: R1 R2 x1 x2)
-struct PairCtxW {
-  PairCtx base;          // the pair's hulls, radii and cylinder sizes (its poses unused)
-  const double* pose;    // the four perturbed poses
-  double cx1[3], cx2[3];  // this lane's group's perturbed centres
-};
-DEVI void mpr_centres(const PairCtxW& c, const Dat&, int, int, double* a, double* b) {
-#pragma unroll
-  for (int k = 0; k < 3; k++) { a[k] = c.cx1[k]; b[k] = c.cx2[k]; }
-}
-DEVI void mink_support(const PairCtxW& c, const double* dir, SupPt* p, unsigned long long act) {
-  const int grp = lane_id() >> 4;
-#pragma unroll 1
-  for (int g = 0; g < 4; g++) {
-    if (!((act >> (16 * g)) & 1ull)) continue;
-    double dg[3] = {readlane_d(dir[0], 16 * g), readlane_d(dir[1], 16 * g), readlane_d(dir[2], 16 * g)};
-    PairCtx q = c.base;
-    const double* P = c.pose + 24 * g;
-#pragma unroll
-    for (int k = 0; k < 9; k++) { q.R1[k] = P[k]; q.R2[k] = P[9 + k]; }
-#pragma unroll
-    for (int k = 0; k < 3; k++) { q.x1[k] = P[18 + k]; q.x2[k] = P[21 + k]; }
-    SupPt t;
-    mink_support(q, dg, &t);
-    if (grp == g) {
-#pragma unroll
-      for (int k = 0; k < 3; k++) { p->a[k] = t.a[k]; p->b[k] = t.b[k]; }
-    }
-  }
-  sub3(p->v, p->a, p->b);
-}
-// The same lockstep MPRs with group-local supports (1, default): every group
-// scans the pair's hulls itself with its 16 lanes, for its own direction and
-// pose, so a lockstep pass is one support call for all four groups instead of
-// up to four whole-wave calls that each load the same vertices again.  Lane li
-// of a group visits vertices li, li + 16, ... in ascending order with a strict
-// '>' (the lowest index of a lane's maxima), the value is max-reduced over the
-// group's DPP row, and the oracle's first maximal vertex is the smallest index
-// among the lanes holding that value: a min-reduction over the row, not the
-// lowest tied lane (lane 1 may hold vertex 17 while lane 2 holds vertex 2) and
-// not a loop over the tied lanes (it would diverge between groups, see
-// ccd_mpr_q).  The context is per lane throughout (hulls, counts, radii and
-// cylinder sizes as well as the pose), so a group could hold a pair of its
-// own; only nmax1 / nmax2, the bounds of the scan loops, are uniform.
-#ifndef MGS_MCCD_G
-#define MGS_MCCD_G 1   // 0: each group's supports by the whole wave in turn (PairCtxW; A/B builds)
-#endif
+// same contacts in the same order.  The supports are group-local (PairCtxG):
+// every group scans the pair's hulls itself with its 16 lanes, for its own
+// direction and pose, so a lockstep pass is one support call for all four
+// groups.  Lane li of a group visits vertices li, li + 16, ... in ascending
+// order with a strict '>' (the lowest index of a lane's maxima), the value is
+// max-reduced over the group's DPP row, and the oracle's first maximal vertex
+// is the smallest index among the lanes holding that value: a min-reduction
+// over the row, not the lowest tied lane (lane 1 may hold vertex 17 while lane
+// 2 holds vertex 2) and not a loop over the tied lanes (it would diverge
+// between groups, see ccd_mpr_q).  The context is per lane throughout (hulls,
+// counts, radii and cylinder sizes as well as the pose), so a group could hold
+// a pair of its own; only nmax1 / nmax2, the bounds of the scan loops, are
+// uniform.
 #ifndef GS_CH
 #define GS_CH 4          // vertices per lane and batch: 3 GS_CH loads issued before the first compare
 #endif
@@ -3303,17 +3264,8 @@ DEVI void multiccd_w(const Mdl& md, Dat& d, int pair, int g1, int g2, const doub
   for (int q = 0; q < 4; q++) mccd_perturb(d, d, g1, g2, n, pos, q, MCCD_POSEW + 24 * q);
   const int lane = lane_id(), grp = lane >> 4;
   {
-#if MGS_MCCD_G
     PairCtxG pc;
     pair_ctxg(md, g1, g2, (const double*)d.poly + MCCD_POSEW + 24 * grp, pc);
-#else
-    PairCtxW pc;
-    pair_ctx(md, d, g1, g2, pc.base);
-    pc.pose = (const double*)d.poly + MCCD_POSEW;
-    const double* P = pc.pose + 24 * grp;
-#pragma unroll
-    for (int k = 0; k < 3; k++) { pc.cx1[k] = P[18 + k]; pc.cx2[k] = P[21 + k]; }
-#endif
     double nn[3], dd = 0.0, pp[3], dir[3] = {0.0, 0.0, 0.0};
     const int hit = ccd_mpr_q(md, d, pc, nn, &dd, pp);
     if ((lane & 15) == 0) mccd_store(d, MCCD_RES + 12 * grp, hit, nn, pp, dir, dd, -1.0);
@@ -3330,26 +3282,16 @@ DEVI void multiccd_w(const Mdl& md, Dat& d, int pair, int g1, int g2, const doub
 // the round instead of one per pair.  collision() runs the round's first MPRs
 // beforehand (their results at MCCD_XRES1 + 12 slot) and emits each pair's
 // contacts afterwards in pair order from the results stored here.
-#ifndef MGS_MCCD_X
-#define MGS_MCCD_X 1   // 0: every pair's multiccd on its own (multiccd_q<8>; A/B builds)
-#endif
 // The context is per lane throughout.  Lane li = lane & 3 of a group holds
-// vertices li and li + 4 of both hulls and scans them in ascending order with
-// a strict '>'; the maximum is reduced over the quad (the two quad_perm DPP
-// levels) and the oracle's first maximal vertex is the smallest index among
-// the lanes holding it, by a min-reduction over the quad as in sup_group
-// (lane 0 may hold vertex 4 while lane 1 holds vertex 1).
-#ifndef MGS_MCCD_XV
-#define MGS_MCCD_XV 1   // 0: the lane's vertices read again at every support (A/B builds)
-#endif
+// vertices li and li + 4 of both hulls (in registers) and scans them in
+// ascending order with a strict '>'; the maximum is reduced over the quad (the
+// two quad_perm DPP levels) and the oracle's first maximal vertex is the
+// smallest index among the lanes holding it, by a min-reduction over the quad
+// as in sup_group (lane 0 may hold vertex 4 while lane 1 holds vertex 1).
 struct PairCtxX {
   int n1, n2;                    // the group's vertex counts
   double R1[9], R2[9], x1[3], x2[3];   // its perturbed poses (x1, x2: also the MPR's centres)
-#if MGS_MCCD_XV
   double v1[2][3], v2[2][3];     // the lane's two vertices of either hull
-#else
-  const double *v1, *v2;         // the hulls' vertices
-#endif
   double r1, r2;                 // rounding radii
 };
 // one geom's pose turned about the first contact pv (pair_ctxq's expressions)
@@ -3375,7 +3317,6 @@ DEVI void pair_ctxx(const Mdl& md, const Dat& d, int pair, const double* n0, con
   c.n2 = hnum[h2];
   const double* V1 = DA(md, hull_vert) + 3 * hadr[h1];
   const double* V2 = DA(md, hull_vert) + 3 * hadr[h2];
-#if MGS_MCCD_XV
 #pragma unroll
   for (int u = 0; u < 2; u++) {
     const int i = li + 4 * u;
@@ -3383,10 +3324,6 @@ DEVI void pair_ctxx(const Mdl& md, const Dat& d, int pair, const double* n0, con
 #pragma unroll
     for (int k = 0; k < 3; k++) { c.v1[u][k] = V1[k * c.n1 + i1]; c.v2[u][k] = V2[k * c.n2 + i2]; }
   }
-#else
-  c.v1 = V1;
-  c.v2 = V2;
-#endif
   c.r1 = DA(md, geom_radius)[g1];
   c.r2 = DA(md, geom_radius)[g2];
   const int ax = q >> 1, sg = q & 1;
@@ -3405,20 +3342,8 @@ DEVI void mpr_centres(const PairCtxX& c, const Dat&, int, int, double* a, double
 }
 // the quad's support vertex of one hull along dl (geom frame, uniform within
 // the quad): oracle support_geom's hull scan
-#if MGS_MCCD_XV
 DEVI void sup_quad(int n, const double (*V)[3], const double* dl, double* v) {
   const int lane = lane_id(), li = lane & 3;
-#else
-DEVI void sup_quad(int n, const double* Vg, const double* dl, double* v) {
-  const int lane = lane_id(), li = lane & 3;
-  double V[2][3];
-#pragma unroll
-  for (int u = 0; u < 2; u++) {
-    const int i = li + 4 * u < n ? li + 4 * u : 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) V[u][k] = Vg[k * n + i];
-  }
-#endif
   SupAcc a;
   sup_init(a);
 #pragma unroll
@@ -3501,10 +3426,10 @@ DEVI int multiccd_x(const Mdl& md, Dat& d, int c0, unsigned long long xall) {
 // convex pairs (ccd_mode 1 / 2; oracle collide_convex_mj): one pair on the
 // whole wave, or two pairs whose hulls fit 16-lane rows at once on the two
 // halves (pairB >= 0); then per pair in order its certificate, first contact
-// and multiccd -- four perturbed MPRs on 16-lane groups when both hulls have
-// at most 8 vertices and no cylinder, else one after another through the
-// whole-wave MPR call site the single pair's first MPR uses (each MPR
-// instance inlined once: more copies spilled the eight-per-CU object).
+// and multiccd: its four perturbed MPRs in lockstep on lane groups -- by
+// multiccd_q<8> when both hulls have at most 8 vertices and no cylinder, else
+// by multiccd_w (each MPR instance inlined once: more copies spilled the
+// eight-per-CU object).
 // collision() has one call site for all of it and splits the pairs of a
 // multiccd_x round (slots xslot, xslot + 1) into stages by xmode:
 //   CX_ALL    first MPR, certificate, first contact and multiccd (every other pair)
@@ -3543,79 +3468,45 @@ DEVI void collide_convex_mj(const Mdl& md, Dat& d, int pairA, int pairB, int mcc
     const int pair = k ? pairB : pairA;
     const int G1 = p1[pair], G2 = p2[pair];
     const bool multi = mccd && md.m.ccd_mode == MGS_CCD_MULTI && IA(md, pair_kind)[pair] == MGS_PAIR_CONVEX;
-    int nc = 0;
-#pragma unroll 1
-    for (int it = 0; it < 5; it++) {
-      if (it > 0 || (pairB < 0 && xmode != CX_EMIT)) {
-        PairCtx pc;
-        if (it > 0) {
-          mccd_perturb(d, d, G1, G2, cp + MCCD_N, cp, it - 1, MCCD_POSE);
-          const double* pz = cp + MCCD_POSE;
-          pair_ctx_pose(md, G1, G2, pz, pz + 18, pz + 9, pz + 21, pc);
-        } else {
-          pair_ctx(md, d, G1, G2, pc);
-        }
-        double n[3], depth, pos[3], cd[3], cm;
-        const int hit = ccd_mpr(md, d, pc, G1, G2, n, &depth, pos, cd, &cm);
-        wsync();
-        if (lane == 0) mccd_store(d, xmode == CX_FIRST ? MCCD_XRES1 + 12 * xslot : MCCD_RES, hit, n, pos, cd, depth, cm);
-        wsync();
-        if (xmode == CX_FIRST) break;
-      }
-      const double* r = it == 0 && xmode == CX_EMIT ? cp + MCCD_XRES1 + 12 * xslot
-                        : it == 0 && pairB >= 0     ? cp + MCCD_RES2 + 12 * k
-                                                    : cp + MCCD_RES;
+    if (pairB < 0 && xmode != CX_EMIT) {
+      // the single pair's first MPR
+      PairCtx pc;
+      pair_ctx(md, d, G1, G2, pc);
+      double n[3], depth, pos[3], cd[3], cm;
+      const int hit = ccd_mpr(md, d, pc, G1, G2, n, &depth, pos, cd, &cm);
+      wsync();
+      if (lane == 0) mccd_store(d, xmode == CX_FIRST ? MCCD_XRES1 + 12 * xslot : MCCD_RES, hit, n, pos, cd, depth, cm);
+      wsync();
+    }
+    if (xmode != CX_FIRST) {
+      const double* r = xmode == CX_EMIT ? cp + MCCD_XRES1 + 12 * xslot
+                        : pairB >= 0     ? cp + MCCD_RES2 + 12 * k
+                                         : cp + MCCD_RES;
       const int hk = r[11] != 0.0;
-      if (it == 0) {
-        PT(4);
-        cert_update(md, d, pair, G1, G2, hk, r + 6, r[10]);
-        PCNT(26, 1);
-        PCNT(27, hk);
-        if (!hk) break;
+      PT(4);
+      cert_update(md, d, pair, G1, G2, hk, r + 6, r[10]);
+      PCNT(26, 1);
+      PCNT(27, hk);
+      if (hk) {
         double t1[3], t2[3];
         make_frame(r, t1, t2);
         if (lane == 0) add_contact(d, ncmax, pair, G1, G2, r + 3, r, t1, t2, -r[9]);
         wsync();
-        if (!multi) break;
-        const int nm1 = hnum[ghull[G1]], nm2 = hnum[ghull[G2]];
-        const bool cyl = cy[2 * G1] > 0.0 || cy[2 * G2] > 0.0;
-        if (xmode == CX_EMIT && xran) {
-          // multiccd_x's four results of this pair, as multiccd_q takes its own
-          double p0[3] = {r[3], r[4], r[5]};
-          mccd_list_init(d, p0);
-          nc = 1;
-          mccd_take_groups(md, d, pair, G1, G2, 4, nc, MCCD_XRES + 48 * xslot);
-          break;
-        }
-        if (MGS_MCCD_Q && !cyl && nm1 <= 8 && nm2 <= 8) {
+        if (multi) {
+          const int nm1 = hnum[ghull[G1]], nm2 = hnum[ghull[G2]];
+          const bool cyl = cy[2 * G1] > 0.0 || cy[2 * G2] > 0.0;
           double n0[3] = {r[0], r[1], r[2]}, p0[3] = {r[3], r[4], r[5]};
-          multiccd_q<8>(md, d, pair, G1, G2, n0, p0);
-          break;
+          if (xmode == CX_EMIT && xran) {
+            // multiccd_x's four results of this pair, as multiccd_q takes its own
+            mccd_list_init(d, p0);
+            int nc = 1;
+            mccd_take_groups(md, d, pair, G1, G2, 4, nc, MCCD_XRES + 48 * xslot);
+          } else if (!cyl && nm1 <= 8 && nm2 <= 8) {
+            multiccd_q<8>(md, d, pair, G1, G2, n0, p0);
+          } else {
+            multiccd_w(md, d, pair, G1, G2, n0, p0);
+          }
         }
-        if (MGS_MCCD_W) {
-          double n0[3] = {r[0], r[1], r[2]}, p0[3] = {r[3], r[4], r[5]};
-          multiccd_w(md, d, pair, G1, G2, n0, p0);
-          break;
-        }
-        // the first contact: the list's first entry and the perturbation frame
-        if (lane == 0) {
-          double* w = (double*)d.poly;
-#pragma unroll
-          for (int i = 0; i < 3; i++) { w[i] = r[3 + i]; w[MCCD_N + i] = r[i]; }
-        }
-        wsync();
-        nc = 1;
-      } else {
-        if (!hk) continue;
-        double pk[3] = {r[3], r[4], r[5]};
-        if (!mccd_is_new(d, nc, pk, mccd_tol(md, G1, G2))) continue;
-        double nk[3] = {r[0], r[1], r[2]};
-        const double dk = r[9];
-        mccd_list_add(d, nc, pk);
-        nc++;
-        double u1[3], u2[3];
-        make_frame(nk, u1, u2);
-        if (lane == 0) add_contact(d, ncmax, pair, G1, G2, pk, nk, u1, u2, -dk);
       }
     }
     wsync();
@@ -4049,7 +3940,7 @@ DEVI void collision(const Mdl& md, Dat& d, int mccd = 1) {
       small2 = n1 <= 16 && n2 <= 16;
       // multiccd_q<8>'s pairs: their multiccd may go several pairs at a time (multiccd_x)
       const double* cy = DA(md, geom_cyl);
-      xel = MGS_MCCD_X && MGS_MCCD_Q && mccd && md.m.ccd_mode == MGS_CCD_MULTI && pk == MGS_PAIR_CONVEX &&
+      xel = mccd && md.m.ccd_mode == MGS_CCD_MULTI && pk == MGS_PAIR_CONVEX &&
             n1 <= 8 && n2 <= 8 && !(cy[2 * g[0]] > 0.0 || cy[2 * g[1]] > 0.0);
     }
     const unsigned long long smallm = __ballot(small2);

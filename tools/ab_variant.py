@@ -65,7 +65,7 @@ def main():
         os.makedirs(src)
         os.makedirs(os.path.join(td, "include"))
         shutil.copy(abi.HEADER, os.path.join(td, "include"))
-        for f in os.listdir(special.CSRC):
+        for f in os.listdir(srcdir or special.CSRC):
             shutil.copy(os.path.join(srcdir or special.CSRC, f), src)
         k = os.path.join(src, "mgs_kernels.hip")
         if noinline:
