@@ -7,14 +7,9 @@
 #include <string>
 #include <vector>
 
-#ifdef MGS_WIDE
-#define MGS_RPL 4
-#ifndef MGS_G_LDS          /* -DMGS_G_LDS: the wide build with G kept in LDS (experiments) */
-#define MGS_G_GLOBAL 1
-#endif
-#endif
 #include "mgs_kernels.hip"
 #include "mgs_launch.h"
+#include "mgs_aux.hip"
 #include "mgs_sampler.hip"
 #include "mgs_contact.hip"
 

@@ -7,13 +7,6 @@
 // specialised code object attached (mgs_special.hip) launches that instead.
 #include <hip/hip_runtime.h>
 
-#ifdef MGS_WIDE
-#define MGS_RPL 4
-#ifndef MGS_G_LDS          /* -DMGS_G_LDS: the wide build with G kept in LDS (experiments) */
-#define MGS_G_GLOBAL 1
-#endif
-#endif
-#define MGS_TEMPLATES_ONLY
 #include "mgs_kernels.hip"
 #include "mgs_launch.h"
 

@@ -20,447 +20,8 @@
 // oracle restatement, and the only cross-lane reduction is the pairwise tree
 // of tree_dot(), so fp64 results are bit-identical to the oracle.
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/mgs_gpu.h"
-
-#define K_MINVAL 1e-15
-#define K_MAXF 16
-#define K_MAXPOLY 40
-#define K_POLY_POINTS (4 * K_MAXF + 3 * K_MAXPOLY)   // collide_manifold's polygon scratch
-#define K_MPR_MAXIT 64
-#define K_FEAT_EPS 1e-5
-#define K_BB_MERGE 1e-6     // box-box: merge distance of manifold points, x face half size (oracle BB_MERGE)
-// separation certificates (cert_check): slots per candidate, doubles per slot,
-// the least margin worth keeping and the safety margin of the validity test
-#define K_CERT 8
-#define CERT_W 17
-#define CERT_STORE 1e-6
-#define CERT_EPS 1e-10
-#define WAVE 64
-// row stride of the constraint matrix G (doubles): NV + MGS_GPAD.  With lanes
-// over rows reading G[r * GS + k], an odd stride spreads the 32 lanes of a
-// ds_read_b64 group over distinct banks (pad 1, the default with G in LDS, at
-// the even dof counts of the shipped models).  G rows in HBM are unpadded
-#ifndef MGS_GPAD
-#ifdef MGS_G_GLOBAL
-#define MGS_GPAD 0
-#else
-#define MGS_GPAD 1
-#endif
-#endif
-#define GS (NV + MGS_GPAD)
-#if defined(MGS_G_GLOBAL) && MGS_GPAD != 0
-#error "G rows in HBM are unpadded (launch_layout sizes them nefc_max * nv)"
-#endif
-#define DEVI __device__ __attribute__((always_inline)) inline
-
-struct P2 { double x, y, h; };
-
-// ---------------------------------------------------------------------------
-// model access
-struct Mdl {
-  mgs_model_desc m;
-  const int32_t* I;
-  const double* D;
-};
-#define IA(md, f) ((md).I + (md).m.i_##f)
-#define DA(md, f) ((md).D + (md).m.d_##f)
-
-// per-candidate working set in LDS (see make_layout in mgs_capi.hip for the
-// carve-up; the U region is time-multiplexed between pipeline stages)
-struct Dat {
-  double *qpos, *qvel, *qacc_ws, *ctrl, *mocap_pos, *mocap_quat, *time;
-  double *act, *act_dot;   // actuator state (mujoco.pid setpoint / integral) and its rate (ABI 21)
-  double *xpos, *xquat, *xmat, *xipos, *xanchor, *xaxis;
-  double *subtree_com, *subtree_mass, *cinert, *cdof;
-  double *geom_xpos, *geom_xmat;
-  double *M, *Dv, *Dinv, *sD, *isD, *tmp, *tmp2;
-  double *qfrc_bias, *qfrc_passive, *qfrc_actuator, *qfrc_smooth, *qacc_smooth, *qfrc_constraint;
-  double *act_force, *act_moment, *act_length, *act_vel;
-  double *con_pos, *con_frame, *con_dist;
-  double *efc_R, *efc_b, *con_mu, *con_blk;
-  double* cert;     // separation certificates (K_CERT slots of CERT_W doubles, see cert_check)
-  // U region views
-  double *crb, *cvel, *cacc, *cfrc, *cdof_dot;          // dynamics stage
-  P2* poly;                                           // collision stage
-  double* pdep;                                       // collision stage
-  double *comacc;                                     // comPos stage
-  double *G, *efc_aref, *efc_vel, *efc_pos, *efc_margin, *scratch;  // constraint + solver stage
-  double* qDeriv;                                     // integration stage
-  // Newton solver workspace (U region, after the constraint stage views)
-  double *efc_jar, *efc_jv, *efc_f, *efc_Dr, *efc_isR, *nH, *nw, *nw0, *ng, *ndir, *con_hb;
-  int *con_pair, *con_g1, *con_g2, *efc_type, *efc_dim, *efc_con, *efc_state, *ints;
-  int gs;   // row stride of G (nv + 1)
-};
-// ints[]: 0 ncon, 1 nefc, 2 overflow, 3 iters, 6 cr0, 7 cr1, 8 neq rows, 9 fr0, 10 fr1, 11 lr0, 12 lr1
-#define NCON ints[0]
-#define NEFC ints[1]
-#define OVERFLOW ints[2]
-#define ITERS ints[3]
-// largest contact dimension the kernels handle: 4 (frictionless, sliding,
-// torsional) in the libraries and most specialised objects; 6 (rolling too)
-// in the objects of models with condim-6 pairs (mgs/core/special.py,
-// -DMGS_MAXDIM=6).  Per-contact block storage is MGS_MAXDIM^2 doubles.
-#ifndef MGS_MAXDIM
-#define MGS_MAXDIM 4
-#endif
-static_assert(MGS_MAXDIM == 4 || MGS_MAXDIM == 6, "MGS_MAXDIM is 4 or 6");
-#define BLKSTRIDE (MGS_MAXDIM * MGS_MAXDIM)
-#ifndef MGS_RPL
-#define MGS_RPL 2   // constraint rows per lane (nefc_max <= 64 * MGS_RPL)
-#endif
-// NV-long operand rows of the factor, the triangular solves and the G
-// products held in registers, or read from LDS at each use.  Registers in
-// every build of one dof per lane: the wide flavour's pile objects (nv 38-58,
-// one wave per SIMD) hold them in 424 VGPRs without spilling, and the C5 pile
-// rollout runs 6 % faster for it (round 5, profiles/r05w_c5_register_rows_ab.txt);
-// with two dofs per lane (MGS_DPL 2) each lane has two rows: LDS.  Same values
-// either way.
-#ifndef MGS_REG_ROWS
-#if defined(MGS_DPL) && MGS_DPL > 1
-#define MGS_REG_ROWS 0
-#else
-#define MGS_REG_ROWS 1
-#endif
-#endif
-
-// Packed storage of the mass matrix / its LDL factor and of the Newton
-// Hessian (symmetric; only the lower triangle is ever read): row i of the
-// lower triangle at i (i + 1) / 2 instead of i nv.  The wide build (clutter
-// piles, nv up to 58, whose row loops read M and H from LDS anyway) packs
-// them: 2 x 1653 doubles less at nv 58 (round 5, two pile workgroups per CU);
-// the main build keeps the square layout its register-row factor loads.
-#ifndef MGS_PACKED
-#ifdef MGS_WIDE
-#define MGS_PACKED 1
-#else
-#define MGS_PACKED 0
-#endif
-#endif
-#if MGS_PACKED
-#define TRI(i, k, n) ((((i) * ((i) + 1)) >> 1) + (k))
-#define TRI_SIZE(n) (((n) * ((n) + 1)) >> 1)
-#else
-#define TRI(i, k, n) ((i) * (n) + (k))
-#define TRI_SIZE(n) ((n) * (n))
-#endif
-// (the register-row factor and solves load row i's lower entries by TRI too;
-// the upper ones they load are never used, and TRI keeps them in bounds)
-// the friction coefficients of a contact: its pair's row of the model instead
-// of a per-contact copy in LDS (main-library objects with G in HBM, round 5:
-// the same values -- the copy's one extra slot, mu[dim - 1] = 0, is never read)
-#ifndef MGS_MU_MODEL
-#define MGS_MU_MODEL 0
-#endif
-
-// the lane index through an opaque move at every use: index arithmetic and
-// lane masks derived from it are recomputed where they are used instead of
-// being hoisted out of the step loop and held (in VGPRs, AGPRs and SGPR
-// spill lanes) for the whole rollout (round 5: the headline rollout 430 ->
-// 328 registers with this alone; profiles/r05c_ab.txt)
-DEVI int lane_id() {
-  int l = (int)__lane_id();
-  asm volatile("" : "+v"(l));
-  return l;
-}
-// values that are uniform across the wave but come from LDS: move to SGPRs so
-// control flow on them is scalar
-DEVI int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
-
-// wave-wide shuffle from lane src (0..63): HIP's __shfl(x, src) with width 64
-// (ds_bpermute at byte address 4 src), without its lane-index term, so no
-// per-lane address is derived from the lane index and held across the step loop
-DEVI int shfl(int x, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, x); }
-DEVI double shfl(double x, int src) {
-  const int a = src << 2;
-  const int lo = __builtin_amdgcn_ds_bpermute(a, __double2loint(x));
-  const int hi = __builtin_amdgcn_ds_bpermute(a, __double2hiint(x));
-  return __hiloint2double(hi, lo);
-}
-
-// Diagnostic stage timers (built only with -DMGS_PROFILE; never in the product build)
-#ifdef MGS_PROFILE
-#ifdef MGS_SPECIAL
-// a specialised code object's timers, read by the host with hipModuleGetGlobal
-extern "C" {
-__device__ unsigned long long g_prof[64];
-}
-#else
-// one copy per translation unit (each dof count's kernels, mgs_inst.hip)
-static __device__ unsigned long long g_prof[64];
-#endif
-// per-workgroup accumulators in static LDS; PT(k) at wave-uniform points only
-__shared__ unsigned long long s_prof[67];
-#define PT(k) do { unsigned long long _n = __builtin_amdgcn_s_memtime(); \
-    if (__lane_id() == 0) { s_prof[k] += _n - s_prof[64]; s_prof[64] = _n; } } while (0)
-// slots 61 / 62 at the flush: the workgroup's shader-clock and 100 MHz
-// real-time spans (their ratio is the clock the chip held, MI355X_MICROARCH.md
-// "DVFS give-back" item 6)
-#define PROF_DECL if (__lane_id() == 0) { for (int _k = 0; _k < 64; _k++) s_prof[_k] = 0; \
-    s_prof[64] = s_prof[65] = __builtin_amdgcn_s_memtime(); s_prof[66] = __builtin_amdgcn_s_memrealtime(); }
-#define PROF(k) PT(k)
-#define PCNT(k, v) do { if (__lane_id() == 0) s_prof[k] += (v); } while (0)
-#define PROF_FLUSH if (lane_id() == 0) { \
-    s_prof[61] = __builtin_amdgcn_s_memtime() - s_prof[65]; \
-    s_prof[62] = __builtin_amdgcn_s_memrealtime() - s_prof[66]; \
-    for (int _k = 0; _k < 64; _k++) atomicAdd(&g_prof[_k], s_prof[_k]); }
-#else
-#define PT(k)
-#define PROF_DECL
-#define PROF(k)
-#define PCNT(k, v)
-#define PROF_FLUSH
-#endif
-// Lane-to-lane hand-off inside the one-wave workgroup.  Main build: every
-// such hand-off goes through LDS, whose operations a wave issues and the LDS
-// processes in order, so a wavefront-scope fence (it keeps the compiler from
-// moving memory operations across it) is enough: +1 % on the bench, -1 % on
-// one API launch (profiles/r04v_wavefront_fence_ab.txt).  Wide build (G in
-// HBM: rows written by lanes over rows and read by lanes over dofs through
-// global memory): the workgroup barrier, which waits for the stores.
-#if defined(MGS_WSYNC_FENCE) || (!defined(MGS_G_GLOBAL) && !defined(MGS_WSYNC_BARRIER))
-DEVI void wsync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
-#else
-DEVI void wsync() { __syncthreads(); }
-#endif
-
-// ---------------------------------------------------------------------------
-// math primitives: identical expressions to the oracle
-DEVI void k_sincos(double x, double* s, double* c) {
-  const double inv_pio2 = 6.36619772367581382433e-01;
-  const double pio2_1 = 1.57079632673412561417e+00;
-  const double pio2_1t = 6.07710050650619224932e-11;
-  const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03,
-               S3 = -1.98412698298579493134e-04, S4 = 2.75573137070700676789e-06,
-               S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
-  const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03,
-               C3 = 2.48015872894767294178e-05, C4 = -2.75573143513906633035e-07,
-               C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
-  double kd = x * inv_pio2;
-  kd = (kd >= 0.0) ? floor(kd + 0.5) : -floor(0.5 - kd);
-  double r = (x - kd * pio2_1) - kd * pio2_1t;
-  double z = r * r;
-  double ps = S1 + z * (S2 + z * (S3 + z * (S4 + z * (S5 + z * S6))));
-  double sr = r + (r * z) * ps;
-  double pc = C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6))));
-  double cr = (1.0 - 0.5 * z) + (z * z) * pc;
-  long k = (long)kd;
-  int q = (int)(k & 3);
-  if (q == 0) { *s = sr; *c = cr; }
-  else if (q == 1) { *s = cr; *c = -sr; }
-  else if (q == 2) { *s = -sr; *c = -cr; }
-  else { *s = -cr; *c = sr; }
-}
-
-DEVI double dot3(const double* a, const double* b) {
-  return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
-}
-DEVI void cross3(double* r, const double* a, const double* b) {
-  double r0 = a[1] * b[2] - a[2] * b[1];
-  double r1 = a[2] * b[0] - a[0] * b[2];
-  double r2 = a[0] * b[1] - a[1] * b[0];
-  r[0] = r0; r[1] = r1; r[2] = r2;
-}
-DEVI void sub3(double* r, const double* a, const double* b) {
-  r[0] = a[0] - b[0]; r[1] = a[1] - b[1]; r[2] = a[2] - b[2];
-}
-DEVI void add3(double* r, const double* a, const double* b) {
-  r[0] = a[0] + b[0]; r[1] = a[1] + b[1]; r[2] = a[2] + b[2];
-}
-DEVI void mulmv3(double* r, const double* m, const double* v) {
-  double r0 = (m[0] * v[0] + m[1] * v[1]) + m[2] * v[2];
-  double r1 = (m[3] * v[0] + m[4] * v[1]) + m[5] * v[2];
-  double r2 = (m[6] * v[0] + m[7] * v[1]) + m[8] * v[2];
-  r[0] = r0; r[1] = r1; r[2] = r2;
-}
-DEVI void mulmtv3(double* r, const double* m, const double* v) {
-  double r0 = (m[0] * v[0] + m[3] * v[1]) + m[6] * v[2];
-  double r1 = (m[1] * v[0] + m[4] * v[1]) + m[7] * v[2];
-  double r2 = (m[2] * v[0] + m[5] * v[1]) + m[8] * v[2];
-  r[0] = r0; r[1] = r1; r[2] = r2;
-}
-DEVI void quatmul(double* r, const double* a, const double* b) {
-  double r0 = ((a[0] * b[0] - a[1] * b[1]) - a[2] * b[2]) - a[3] * b[3];
-  double r1 = ((a[0] * b[1] + a[1] * b[0]) + a[2] * b[3]) - a[3] * b[2];
-  double r2 = ((a[0] * b[2] - a[1] * b[3]) + a[2] * b[0]) + a[3] * b[1];
-  double r3 = ((a[0] * b[3] + a[1] * b[2]) - a[2] * b[1]) + a[3] * b[0];
-  r[0] = r0; r[1] = r1; r[2] = r2; r[3] = r3;
-}
-DEVI void quat2mat(double* m, const double* q) {
-  double q00 = q[0] * q[0], q01 = q[0] * q[1], q02 = q[0] * q[2], q03 = q[0] * q[3];
-  double q11 = q[1] * q[1], q12 = q[1] * q[2], q13 = q[1] * q[3];
-  double q22 = q[2] * q[2], q23 = q[2] * q[3], q33 = q[3] * q[3];
-  m[0] = ((q00 + q11) - q22) - q33;
-  m[1] = 2.0 * (q12 - q03);
-  m[2] = 2.0 * (q13 + q02);
-  m[3] = 2.0 * (q12 + q03);
-  m[4] = ((q00 - q11) + q22) - q33;
-  m[5] = 2.0 * (q23 - q01);
-  m[6] = 2.0 * (q13 - q02);
-  m[7] = 2.0 * (q23 + q01);
-  m[8] = ((q00 - q11) - q22) + q33;
-}
-DEVI void normalize4(double* q) {
-  double n = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-  if (n < K_MINVAL) { q[0] = 1.0; q[1] = q[2] = q[3] = 0.0; return; }
-  double inv = 1.0 / n;
-  q[0] = q[0] * inv; q[1] = q[1] * inv; q[2] = q[2] * inv; q[3] = q[3] * inv;
-}
-DEVI double normalize3(double* v) {
-  double n = sqrt(dot3(v, v));
-  if (n < K_MINVAL) { v[0] = 1.0; v[1] = v[2] = 0.0; return 0.0; }
-  double inv = 1.0 / n;
-  v[0] = v[0] * inv; v[1] = v[1] * inv; v[2] = v[2] * inv;
-  return n;
-}
-DEVI void axisangle2quat(double* q, const double* axis, double angle) {
-  double s, c;
-  k_sincos(0.5 * angle, &s, &c);
-  q[0] = c; q[1] = axis[0] * s; q[2] = axis[1] * s; q[3] = axis[2] * s;
-}
-DEVI void mul_inert_vec(double* r, const double* i, const double* v) {
-  double r0 = ((i[0] * v[0] + i[3] * v[1]) + i[4] * v[2]) - i[8] * v[4] + i[7] * v[5];
-  double r1 = ((i[3] * v[0] + i[1] * v[1]) + i[5] * v[2]) + i[8] * v[3] - i[6] * v[5];
-  double r2 = ((i[4] * v[0] + i[5] * v[1]) + i[2] * v[2]) - i[7] * v[3] + i[6] * v[4];
-  double r3 = (i[8] * v[1] - i[7] * v[2]) + i[9] * v[3];
-  double r4 = (i[6] * v[2] - i[8] * v[0]) + i[9] * v[4];
-  double r5 = (i[7] * v[0] - i[6] * v[1]) + i[9] * v[5];
-  r[0] = r0; r[1] = r1; r[2] = r2; r[3] = r3; r[4] = r4; r[5] = r5;
-}
-DEVI double dot6(const double* a, const double* b) {
-  return ((((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3]) + a[4] * b[4]) + a[5] * b[5];
-}
-DEVI void cross_motion(double* r, const double* v, const double* u) {
-  double r0 = v[1] * u[2] - v[2] * u[1];
-  double r1 = v[2] * u[0] - v[0] * u[2];
-  double r2 = v[0] * u[1] - v[1] * u[0];
-  double r3 = (v[1] * u[5] - v[2] * u[4]) + (v[4] * u[2] - v[5] * u[1]);
-  double r4 = (v[2] * u[3] - v[0] * u[5]) + (v[5] * u[0] - v[3] * u[2]);
-  double r5 = (v[0] * u[4] - v[1] * u[3]) + (v[3] * u[1] - v[4] * u[0]);
-  r[0] = r0; r[1] = r1; r[2] = r2; r[3] = r3; r[4] = r4; r[5] = r5;
-}
-DEVI void cross_force(double* r, const double* v, const double* f) {
-  double r0 = (v[1] * f[2] - v[2] * f[1]) + (v[4] * f[5] - v[5] * f[4]);
-  double r1 = (v[2] * f[0] - v[0] * f[2]) + (v[5] * f[3] - v[3] * f[5]);
-  double r2 = (v[0] * f[1] - v[1] * f[0]) + (v[3] * f[4] - v[4] * f[3]);
-  double r3 = v[1] * f[5] - v[2] * f[4];
-  double r4 = v[2] * f[3] - v[0] * f[5];
-  double r5 = v[0] * f[4] - v[1] * f[3];
-  r[0] = r0; r[1] = r1; r[2] = r2; r[3] = r3; r[4] = r4; r[5] = r5;
-}
-
-// Pairwise tree reduction over lanes, identical to the oracle's tree_dot():
-// level s (s = 1, 2, 4, ... < P) adds lane k^s to lane k.  Within a 16-lane row
-// the levels are DPP moves (xor 1 and xor 2 by quad permutes; xor 4 and xor 8 by
-// the half-row / row mirrors, which equal xor on values already uniform over
-// the lower levels); the last two levels combine the four row sums read with
-// v_readlane in the same pairing ((r0 + r1) + (r2 + r3)).  Result is uniform.
-DEVI double dpp_d(double x, int ctrl_sel) {
-  int lo = __double2loint(x), hi = __double2hiint(x);
-  switch (ctrl_sel) {
-    case 0: lo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, false); hi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, false); break;
-    case 1: lo = __builtin_amdgcn_mov_dpp(lo, 0x4E, 0xF, 0xF, false); hi = __builtin_amdgcn_mov_dpp(hi, 0x4E, 0xF, 0xF, false); break;
-    case 2: lo = __builtin_amdgcn_mov_dpp(lo, 0x141, 0xF, 0xF, false); hi = __builtin_amdgcn_mov_dpp(hi, 0x141, 0xF, 0xF, false); break;
-    default: lo = __builtin_amdgcn_mov_dpp(lo, 0x140, 0xF, 0xF, false); hi = __builtin_amdgcn_mov_dpp(hi, 0x140, 0xF, 0xF, false); break;
-  }
-  return __hiloint2double(hi, lo);
-}
-DEVI double readlane_d(double x, int l) {
-  int lo = __builtin_amdgcn_readlane(__double2loint(x), l);
-  int hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
-  return __hiloint2double(hi, lo);
-}
-DEVI double tree_sum(double leaf, int P) {
-  if (P > 1) leaf = leaf + dpp_d(leaf, 0);
-  if (P > 2) leaf = leaf + dpp_d(leaf, 1);
-  if (P > 4) leaf = leaf + dpp_d(leaf, 2);
-  if (P > 8) leaf = leaf + dpp_d(leaf, 3);
-  if (P > 16) {
-    double r0 = readlane_d(leaf, 0), r1 = readlane_d(leaf, 16);
-    if (P > 32) {
-      double r2 = readlane_d(leaf, 32), r3 = readlane_d(leaf, 48);
-      return (r0 + r1) + (r2 + r3);
-    }
-    return r0 + r1;
-  }
-  return readlane_d(leaf, 0);
-}
-DEVI int next_pow2(int n) {
-  int P = 1;
-  while (P < n) P <<= 1;
-  return P;
-}
-
-// Dofs per lane.  Lanes over dofs is the unit of the dynamics, the solves and
-// the solver sweeps: lane l owns dof l (MGS_DPL 1, every library build and
-// every model of at most 64 dofs) or dofs l and l + 64 (MGS_DPL 2: the
-// specialised objects of models with 65-128 dofs, clutter piles of 7-10
-// objects).  A dof-indexed value held in registers is a DofV; with MGS_DPL 1
-// every helper below is the single-slot expression it replaces.
-#ifndef MGS_DPL
-#define MGS_DPL 1
-#endif
-static_assert(MGS_DPL == 1 || MGS_DPL == 2, "MGS_DPL is 1 or 2");
-static_assert(MGS_DPL == 1 || (MGS_PACKED && !MGS_REG_ROWS), "two dofs per lane: the wide flavour (MGS_WIDE)");
-#define MGS_MAXNV (WAVE * MGS_DPL)
-struct DofV {
-  double v[MGS_DPL];
-};
-DEVI DofV dof_zero() {
-  DofV x;
-#pragma unroll
-  for (int h = 0; h < MGS_DPL; h++) x.v[h] = 0.0;
-  return x;
-}
-// p[dof] on the dof's lane, 0 past nv
-DEVI DofV dof_load(const double* p, int nv, int lane) {
-  DofV x;
-#pragma unroll
-  for (int h = 0; h < MGS_DPL; h++) x.v[h] = (lane + h * WAVE < nv) ? p[lane + h * WAVE] : 0.0;
-  return x;
-}
-DEVI DofV dof_mul(const DofV& a, const DofV& b) {
-  DofV x;
-#pragma unroll
-  for (int h = 0; h < MGS_DPL; h++) x.v[h] = a.v[h] * b.v[h];
-  return x;
-}
-// the oracle's tree_dot over the dof leaves (P = next_pow2(nv)): a tree over
-// 128 leaves is the tree over dofs 0-63 plus the tree over dofs 64-127 (its
-// last level adds leaf 64 to leaf 0)
-DEVI double dof_tree(const DofV& x, int P) {
-  if (MGS_DPL == 1 || P <= WAVE) return tree_sum(x.v[0], P);
-  return tree_sum(x.v[0], WAVE) + tree_sum(x.v[MGS_DPL - 1], WAVE);
-}
-// u += g delta on the lanes' dofs below nv (the others keep their value)
-DEVI void dof_axpy(DofV& u, const DofV& g, double delta, int nv, int lane) {
-#pragma unroll
-  for (int h = 0; h < MGS_DPL; h++) {
-    double s = u.v[h] + g.v[h] * delta;
-    if (lane + h * WAVE < nv) u.v[h] = s;
-  }
-}
-// `DOF_SLOTS(i, nv) stmt;`: stmt for each dof i < nv of this lane (lane, lane + 64)
-#define DOF_SLOTS(i, nv) \
-  _Pragma("unroll") for (int _h = 0, i = lane + 0; _h < MGS_DPL; _h++, i += WAVE) if (i < (nv))
-// dof k's value, uniform (k uniform)
-DEVI double dof_readlane(const DofV& x, int k) {
-  if (MGS_DPL == 1) return readlane_d(x.v[0], k);
-  return readlane_d((k >> 6) ? x.v[MGS_DPL - 1] : x.v[0], k & (WAVE - 1));
-}
-// dof col moves body b: the model's body_dofmask, bit col of the body's words
-// (2 words per body, 4 for models of more than 64 dofs; mgs_gpu.h)
-DEVI int dof_moves(const Mdl& md, int b, int col) {
-  if (MGS_DPL == 1) {
-    const int32_t* mask = IA(md, body_dofmask) + 2 * b;
-    return (col < 32) ? ((mask[0] >> col) & 1) : ((mask[1] >> (col - 32)) & 1);
-  }
-  const int32_t* mask = IA(md, body_dofmask) + (md.m.nv > 64 ? 4 : 2) * b;
-  return (mask[col >> 5] >> (col & 31)) & 1;
-}
-
+#include "mgs_k_base.h"
+#include "mgs_k_math.h"
 // ---------------------------------------------------------------------------
 // Tree-level parallel forward kinematics (oracle kinematics()): lane b owns
 // body b; bodies of one tree depth are independent given their parents, so the
@@ -4000,168 +3561,7 @@ DEVI void collision(const Mdl& md, Dat& d, int mccd = 1) {
   }
 }
 
-// ---------------------------------------------------------------------------
-// LDS layout (offsets in doubles; computed on the host by make_layout)
-// LDS carve-up (make_layout in mgs_capi.hip).  Persistent arrays live for the
-// whole step; the U region is time-multiplexed between stages:
-//   kin/collision: polygon buffers, geom poses, xipos/xanchor/xaxis, comPos sums
-//   dynamics:      crb | cvel, cacc, cfrc, cdof_dot, qfrc_bias/passive/actuator
-//   constraints:   G, aref, {vel,pos,margin | Newton Hessian}, scratch, Newton rows
-//   integration:   qDeriv
-enum {
-  L_qpos, L_qvel, L_qacc_ws, L_ctrl, L_mocap_pos, L_mocap_quat, L_time, L_act, L_act_dot,
-  L_xpos, L_xquat, L_xmat, L_subtree_com, L_cinert, L_cdof,
-  L_M, L_Dv, L_Dinv, L_sD, L_isD, L_tmp, L_tmp2,
-  L_qfrc_smooth, L_qacc_smooth, L_qfrc_constraint,
-  L_act_force, L_act_moment, L_act_length, L_act_vel,
-  L_con_pos, L_con_frame, L_con_dist, L_con_mu, L_con_blk,
-  L_efc_R, L_efc_b, L_cert,
-  L_U, L_ints, L_COUNT
-};
-enum {
-  U_poly, U_pdep, U_geom_xpos, U_geom_xmat, U_xipos, U_xanchor, U_xaxis, U_subtree_mass, U_comacc,
-  U_crb, U_cvel, U_cacc, U_cfrc, U_cdof_dot, U_qfrc_bias, U_qfrc_passive, U_qfrc_actuator,
-  U_G, U_aref, U_vel, U_pos, U_margin, U_nH, U_scratch, U_jar, U_jv, U_f, U_Dr, U_isR, U_nw, U_nw0, U_ng,
-  U_ndir, U_qDeriv, U_COUNT
-};
-// doubles of one candidate's HBM slice (G rows, and with MGS_HBM_EXTRA the
-// certificates, contact frames and contact blocks); mgs_capi.hip's hbm_slice
-// allocates the same
-#ifndef MGS_HBM_EXTRA
-#define MGS_HBM_EXTRA 0
-#endif
-// ... and a copy of the unfactored M for integrate (m_copy_slot), so the step
-// computes crb() once.  MGS_M_KEEP 0 recomputes (A/B builds; the slice keeps
-// its size: the host sizes it without knowing the object's switch)
-#ifndef MGS_M_KEEP
-#define MGS_M_KEEP 1
-#endif
-DEVI size_t hbm_slice(int ne, int nv, int nc) {
-  return (size_t)ne * nv +
-         (MGS_HBM_EXTRA ? (size_t)(K_CERT * CERT_W + 9 * nc + BLKSTRIDE * nc + TRI_SIZE(nv)) : 0);
-}
-struct Lay {
-  int o[L_COUNT];
-  int u[U_COUNT];   // offsets relative to o[L_U]
-  int ncon_max, nefc_max, nv;
-  int total_doubles;
-  double* gmem;     // MGS_G_GLOBAL: per-candidate G rows in HBM (nefc_max * nv doubles each)
-};
-
-// Model specialisation: a code object compiled for one model (mgs_special.hip
-// with the header mgs.core.special generates for it, -DMGS_SPECIAL=<header>)
-// carries that model's LDS carve-up and description as compile-time constants.
-// A kernel instantiated with SL = 1 binds every view at a constant LDS address,
-// so the ~80 views need no SGPRs (their spills to VGPR lanes and reloads
-// disappear), LDS accesses carry their offsets as instruction immediates, and
-// sizes / table offsets / options are constants (trip counts, immediates).
-// The host attaches such an object to a model only after comparing the
-// object's baked description and layout with the model's
-// (mgs_model_attach_special).
-#ifdef MGS_SPECIAL
-#include MGS_SPECIAL
-static_assert(MGS_SL_ABI == MGS_ABI_VERSION, "specialisation header of another ABI version: regenerate it");
-static_assert(MGS_SL_DESC_BYTES == sizeof(mgs_model_desc), "specialisation header of another mgs_model_desc");
-#else
-#define MGS_SL_NV 0
-constexpr int mgs_sl_words[L_COUNT + U_COUNT + 4] = {0};
-constexpr mgs_model_desc mgs_sl_desc = {};
-#endif
-static_assert(sizeof(mgs_sl_words) == sizeof(int) * (L_COUNT + U_COUNT + 4), "specialised layout size");
-
-template <int SL>
-DEVI void bind(Dat& d, double* s, const Lay& l) {
-#define LO(k) (SL ? mgs_sl_words[k] : l.o[k])
-#define LU(k) (SL ? mgs_sl_words[L_COUNT + (k)] : l.u[k])
-#define B(f) d.f = s + LO(L_##f)
-  B(qpos); B(qvel); B(qacc_ws); B(ctrl); B(mocap_pos); B(mocap_quat); B(time); B(act); B(act_dot);
-  B(xpos); B(xquat); B(xmat); B(subtree_com); B(cinert); B(cdof);
-  B(M); B(Dv); B(Dinv); B(sD); B(isD); B(tmp); B(tmp2);
-  B(qfrc_smooth); B(qacc_smooth); B(qfrc_constraint);
-  B(act_force); B(act_moment); B(act_length); B(act_vel);
-  B(con_pos); B(con_frame); B(con_dist); B(con_mu); B(con_blk);
-  B(efc_R); B(efc_b); B(cert);
-#undef B
-  double* U = s + LO(L_U);
-#define BU(f, k) d.f = U + LU(k)
-  d.poly = (P2*)(U + LU(U_poly));
-  BU(pdep, U_pdep); BU(geom_xpos, U_geom_xpos); BU(geom_xmat, U_geom_xmat); BU(xipos, U_xipos);
-  BU(xanchor, U_xanchor); BU(xaxis, U_xaxis); BU(subtree_mass, U_subtree_mass); BU(comacc, U_comacc);
-  BU(crb, U_crb); BU(cvel, U_cvel); BU(cacc, U_cacc); BU(cfrc, U_cfrc); BU(cdof_dot, U_cdof_dot);
-  BU(qfrc_bias, U_qfrc_bias); BU(qfrc_passive, U_qfrc_passive); BU(qfrc_actuator, U_qfrc_actuator);
-#ifdef MGS_G_GLOBAL
-  // wide library (clutter piles): G = D^-1/2 L^-1 J' is too large for LDS at
-  // nefc_max 256 x nv 58; it lives in this candidate's HBM slice (L2-cached).
-  // Main-library objects with G in HBM (MGS_HBM_EXTRA) keep the separation
-  // certificates, the contact frames and the contact blocks there too.
-  {
-    const int sl_nc = SL ? mgs_sl_words[L_COUNT + U_COUNT] : l.ncon_max;
-    const int sl_ne = SL ? mgs_sl_words[L_COUNT + U_COUNT + 1] : l.nefc_max;
-    const int sl_nv = SL ? mgs_sl_words[L_COUNT + U_COUNT + 2] : l.nv;
-    d.G = l.gmem + (size_t)blockIdx.x * hbm_slice(sl_ne, sl_nv, sl_nc);
-#if MGS_HBM_EXTRA
-    double* x = d.G + (size_t)sl_ne * sl_nv;
-    d.cert = x;
-    x += K_CERT * CERT_W;
-    d.con_frame = x;
-    x += 9 * sl_nc;
-    d.con_blk = x;
-#endif
-  }
-#else
-  BU(G, U_G);
-#endif
-  BU(efc_aref, U_aref); BU(efc_vel, U_vel); BU(efc_pos, U_pos); BU(efc_margin, U_margin);
-  BU(nH, U_nH); BU(scratch, U_scratch); BU(efc_jar, U_jar); BU(efc_jv, U_jv); BU(efc_f, U_f);
-  BU(efc_Dr, U_Dr); BU(efc_isR, U_isR); BU(nw, U_nw); BU(nw0, U_nw0); BU(ng, U_ng); BU(ndir, U_ndir);
-  BU(qDeriv, U_qDeriv);
-#undef BU
-  d.con_hb = d.con_blk;   // Newton cone Hessians reuse the contact-block slots
-  d.gs = (SL ? mgs_sl_words[L_COUNT + U_COUNT + 2] : l.nv) + MGS_GPAD;
-  int* ib = (int*)(s + LO(L_ints));
-  d.ints = ib;
-  int ncmax = SL ? mgs_sl_words[L_COUNT + U_COUNT] : l.ncon_max;
-  int nemax = SL ? mgs_sl_words[L_COUNT + U_COUNT + 1] : l.nefc_max;
-  d.con_pair = ib + 16;
-  d.con_g1 = d.con_pair + ncmax;
-  d.con_g2 = d.con_g1 + ncmax;
-  d.efc_type = d.con_g2 + ncmax;
-  d.efc_dim = d.efc_type + nemax;
-  d.efc_con = d.efc_dim + nemax;
-  d.efc_state = d.efc_con + nemax;
-#undef LO
-#undef LU
-}
-
-// A_rr = G_r . G_r in the oracle's order (its efc_A)
-DEVI double row_sqnorm(const Dat& d, int r, int nv) {
-  const double* Gr = d.G + r * d.gs;
-  double a = 0.0;
-  for (int k = 0; k < nv; k++) a = a + Gr[k] * Gr[k];
-  return a;
-}
-
-// first row of its block (contacts span dim rows with one efc_con)
-DEVI int efc_lead(const Dat& d, int r) {
-  return d.efc_type[r] != MGS_EFC_CONTACT || r == 0 || d.efc_type[r - 1] != MGS_EFC_CONTACT ||
-         d.efc_con[r - 1] != d.efc_con[r];
-}
-
-// contact c's friction coefficients (see MGS_MU_MODEL)
-DEVI const double* con_mu_of(const Mdl& md, const Dat& d, int c) {
-#if MGS_MU_MODEL
-  return DA(md, pair_friction) + 5 * d.con_pair[c];
-#else
-  (void)md;
-  return d.con_mu + 5 * c;
-#endif
-}
-
-// frictionloss of a FRICTION row (its efc_con is the dof), 0 otherwise
-DEVI double row_floss(const Mdl& md, const Dat& d, int r) {
-  return d.efc_type[r] == MGS_EFC_FRICTION ? DA(md, dof_frictionloss)[d.efc_con[r]] : 0.0;
-}
-
+#include "mgs_k_layout.h"
 // ---------------------------------------------------------------------------
 // constraints
 DEVI void jac_point(const Mdl& md, const Dat& d, int b, const double* pt, double* jacp, double* jacr) {
@@ -7102,38 +6502,3 @@ mgs_rollout_kernel(Mdl mdarg, const int32_t* __restrict__ mI, const double* __re
                         label, fail_step, obj_qpos, stats, vstate_init, state_out, list, list_count, resume_out,
                         resume_in, mask_mpos, mask_pred, mask_out, queue, ovf_count, ovf_list);
 }
-
-// the library's non-template kernels live in the C-ABI translation unit only
-// (the per-dof-count units and specialised code objects define MGS_TEMPLATES_ONLY)
-#ifndef MGS_TEMPLATES_ONLY
-// capacity-escalation list: indices of the candidates whose stats flags meet
-// mask (order of arrival; each re-run is independent of the order)
-__global__ void __launch_bounds__(256)
-mgs_overflow_list_kernel(const int32_t* __restrict__ stats, int n, int mask, int32_t* __restrict__ count,
-                         int32_t* __restrict__ list) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && (stats[MGS_NSTATS * i + 2] & mask)) list[atomicAdd(count, 1)] = i;
-}
-
-// device-side arithmetic probe (tests): sqrt, division, sincos against the oracle
-extern "C" __global__ void mgs_arith_probe_kernel(const double* x, const double* y, int n, double* out) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double s, c;
-  k_sincos(x[i], &s, &c);
-  out[4 * i] = sqrt(fabs(x[i]));
-  out[4 * i + 1] = x[i] / y[i];
-  out[4 * i + 2] = s;
-  out[4 * i + 3] = c;
-}
-
-// tree-reduction probe (tests): out[b] = tree_sum over lanes of a[b*64+l]*c[b*64+l] with P = nextpow2(n)
-extern "C" __global__ void __launch_bounds__(64) mgs_tree_probe_kernel(const double* a, const double* c, int n,
-                                                                         double* out) {
-  int l = lane_id();
-  int b = blockIdx.x;
-  double leaf = (l < n) ? a[b * 64 + l] * c[b * 64 + l] : 0.0;
-  double s = tree_sum(leaf, next_pow2(n));
-  if (l == 0) out[b] = s;
-}
-#endif  // MGS_TEMPLATES_ONLY

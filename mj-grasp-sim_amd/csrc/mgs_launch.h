@@ -1,8 +1,9 @@
 // mgs_launch.h -- host-side launch interface between the C-ABI translation unit
 // (mgs_capi.hip) and the per-dof-count kernel instantiations (mgs_inst.hip),
-// which are compiled as separate translation units in parallel.  Include after
-// mgs_kernels.hip (Mdl, Lay).
+// which are compiled as separate translation units in parallel.
 #pragma once
+#include "mgs_k_base.h"
+#include "mgs_k_layout.h"
 
 struct CollisionArgs {
   Mdl md;

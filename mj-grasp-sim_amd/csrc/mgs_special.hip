@@ -15,11 +15,6 @@
 // piles of any size, other grippers) run through these objects.
 #include <hip/hip_runtime.h>
 
-#ifdef MGS_WIDE
-#define MGS_RPL 4
-#define MGS_G_GLOBAL 1
-#endif
-#define MGS_TEMPLATES_ONLY
 #include "mgs_kernels.hip"
 
 #ifndef MGS_SPECIAL

@@ -4,11 +4,15 @@ test of the libraries' per-unit objects (__graft_entry__._library_jobs).  Both
 derive their lists from the quoted #includes of the translation units; a file
 missing from either would mean stale objects reused after an edit.  The case
 that matters -- a header added to the kernel source -- is played through on a
-copy of csrc/ and include/.  No compiler run, no library.
+copy of csrc/ and include/.  The stage headers that mgs_kernels.hip includes
+(mgs_k_*.h) include what they use: each alone passes the compiler's
+device-side syntax check (about a second each; the only compiler run here).
+No library, nothing on the GPU.
 """
 import os
 import re
 import shutil
+import subprocess
 
 import pytest
 
@@ -132,7 +136,7 @@ def test_a_byte_in_any_source_changes_the_key(source_copy, source, no_compiler):
 
 
 # where a header added to the kernel source may be included from
-INCLUDERS = ["mgs_kernels.hip", "mgs_launch.h", "../../include/mgs_gpu.h"]
+INCLUDERS = ["mgs_kernels.hip", "mgs_k_math.h", "mgs_launch.h", "../../include/mgs_gpu.h"]
 
 
 @pytest.mark.parametrize("includer", INCLUDERS)
@@ -169,6 +173,45 @@ def test_a_kernel_header_nobody_includes_is_reported(tmp_path):
         f.write("#pragma once\n")
     with pytest.raises(AssertionError, match="mgs_k_orphan.h is not reached"):
         check_unit_closure("mgs_inst.hip", csrc)
+
+
+STAGE_HEADERS = sorted(f for f in os.listdir(special.CSRC) if f.startswith("mgs_k_") and f.endswith(".h"))
+
+
+def test_every_stage_header_is_included_once_by_the_kernel_source():
+    """mgs_kernels.hip includes each mgs_k_*.h of csrc/ itself, exactly once, so
+    the order of definitions is the order of its include lines"""
+    assert STAGE_HEADERS
+    included = quoted_includes(os.path.join(special.CSRC, "mgs_kernels.hip"))
+    for h in STAGE_HEADERS:
+        assert included.count(h) == 1, h
+
+
+def _hipcc():
+    for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc")):
+        if c and os.path.isfile(c):
+            return c
+    return None
+
+
+@pytest.mark.parametrize("flavour", [[], ["-DMGS_WIDE"]], ids=["main", "wide"])
+@pytest.mark.parametrize("header", STAGE_HEADERS)
+def test_a_stage_header_compiles_alone(source_copy, tmp_path, header, flavour):
+    """a unit of one line, the header's include, passes the device-side syntax
+    check: the header includes what it uses"""
+    hipcc = _hipcc()
+    if hipcc is None:
+        pytest.skip("no hipcc")
+    unit = os.path.join(source_copy, f"alone_{os.path.basename(str(tmp_path))}.hip")
+    with open(unit, "w") as f:
+        f.write(f'#include "{header}"\n')
+    try:
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-fsyntax-only",
+                            *flavour, "-I", os.path.join(os.path.dirname(os.path.dirname(source_copy)), "include"),
+                            unit], capture_output=True, text=True)
+    finally:
+        os.remove(unit)
+    assert r.returncode == 0, r.stderr[-3000:]
 
 
 @pytest.mark.parametrize("closure", [special.include_closure, entry._include_closure])

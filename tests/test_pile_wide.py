@@ -4,7 +4,7 @@ The reference draws piles of `num_objects_min`..`num_objects_max` objects with
 repetition (mgs/obj/selector.py:124-130); with the Shadow hand (28 dofs) and
 six per free object, 7 objects give nv 70 and 10 give nv 88 -- past the 64
 lanes of a wave.  Those models run in a specialised code object of the wide
-flavour built with -DMGS_DPL=2 (mgs_kernels.hip DofV: lane l owns dofs l and
+flavour built with -DMGS_DPL=2 (mgs_k_math.h DofV: lane l owns dofs l and
 l + 64; the dof reductions are the oracle's tree_dot over 128 leaves, i.e. the
 tree over each half, then their sum).  The piles here are spread on the table
 (mgs.core.shipped.spread_pile): parity does not need a settled pile.

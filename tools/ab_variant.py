@@ -67,12 +67,13 @@ def main():
         shutil.copy(abi.HEADER, os.path.join(td, "include"))
         for f in os.listdir(srcdir or special.CSRC):
             shutil.copy(os.path.join(srcdir or special.CSRC, f), src)
-        k = os.path.join(src, "mgs_kernels.hip")
         if noinline:
-            s = open(k).read()
             old = "#define DEVI __device__ __attribute__((always_inline)) inline"
-            assert old in s
-            open(k, "w").write(s.replace(old, "#define DEVI __device__ __attribute__((noinline))"))
+            holders = [k for k in (os.path.join(src, f) for f in sorted(os.listdir(src))) if old in open(k).read()]
+            assert len(holders) == 1, holders      # the one definition (mgs_k_base.h)
+            s = open(holders[0]).read()
+            assert s.count(old) == 1
+            open(holders[0], "w").write(s.replace(old, "#define DEVI __device__ __attribute__((noinline))"))
         hp = os.path.join(td, "model.h")
         open(hp, "w").write(header)
         cmd = [special._hipcc(), *flags, *extra, f'-DMGS_SPECIAL="{hp}"', os.path.join(src, "mgs_special.hip"),
