@@ -5,8 +5,9 @@ derive their lists from the quoted #includes of the translation units; a file
 missing from either would mean stale objects reused after an edit.  The case
 that matters -- a header added to the kernel source -- is played through on a
 copy of csrc/ and include/.  The stage headers that mgs_kernels.hip includes
-(mgs_k_*.h) include what they use: each alone passes the compiler's
-device-side syntax check (about a second each; the only compiler run here).
+(mgs_k_*.h), in dependency order, are guarded and include what they use: each
+alone passes the compiler's device-side syntax check (about a second each;
+the only compiler run here).
 No library, nothing on the GPU.
 """
 import os
@@ -136,7 +137,7 @@ def test_a_byte_in_any_source_changes_the_key(source_copy, source, no_compiler):
 
 
 # where a header added to the kernel source may be included from
-INCLUDERS = ["mgs_kernels.hip", "mgs_k_math.h", "mgs_launch.h", "../../include/mgs_gpu.h"]
+INCLUDERS = ["mgs_kernels.hip", "mgs_k_math.h", "mgs_k_constraints.h", "mgs_launch.h", "../../include/mgs_gpu.h"]
 
 
 @pytest.mark.parametrize("includer", INCLUDERS)
@@ -185,6 +186,24 @@ def test_every_stage_header_is_included_once_by_the_kernel_source():
     included = quoted_includes(os.path.join(special.CSRC, "mgs_kernels.hip"))
     for h in STAGE_HEADERS:
         assert included.count(h) == 1, h
+
+
+def test_the_include_order_is_a_dependency_order():
+    """a stage header includes only stage headers that stand before it in
+    mgs_kernels.hip, so every definition is seen at its place in that list
+    whichever header is included first"""
+    order = [h for h in quoted_includes(os.path.join(special.CSRC, "mgs_kernels.hip")) if h in STAGE_HEADERS]
+    assert sorted(order) == STAGE_HEADERS
+    for h in STAGE_HEADERS:
+        for inc in quoted_includes(os.path.join(special.CSRC, h)):
+            if inc in STAGE_HEADERS:
+                assert order.index(inc) < order.index(h), f"{h} includes {inc}, which stands after it"
+
+
+@pytest.mark.parametrize("header", STAGE_HEADERS)
+def test_a_stage_header_is_guarded(header):
+    with open(os.path.join(special.CSRC, header)) as f:
+        assert re.search(r"^#\s*pragma\s+once\s*$", f.read(), re.M), header
 
 
 def _hipcc():
