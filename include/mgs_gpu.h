@@ -656,6 +656,76 @@ int mgs_contact_optimize(int device, const mgs_kin_desc* kin, int n, const doubl
                          const double* targets, const double* normals, double* out_rot, double* out_pos,
                          double* out_joints, double* out_loss, double* kernel_ms);
 
+/* ---------------------------------------------------------------------------
+ * Scene scan (MjScanEnv.scan, mgs/env/base.py:77-126; rgbd_to_pcd,
+ * mgs/util/img_proc.py:38-62): depth, geom segmentation and points of a
+ * clutter scene by ray casting, geometry only.  Additive entries (no struct
+ * above changes; the ABI version stays).  Host pointers, synchronous on
+ * `device`; kernel_ms (may be NULL) = kernel duration.
+ *
+ * A scene is a list of drawables -- boxes and spheres given by pose and size,
+ * mesh instances given by pose and a mesh index -- and, per distinct mesh, a
+ * threaded bounding-volume hierarchy: the nodes of mesh m are
+ * mesh_node0[m] .. mesh_node0[m + 1] - 1 in depth-first order, so node i + 1 is
+ * the first child of an inner node i (node_count == 0) and node_skip[i] (an
+ * index within the mesh, i < skip <= the mesh's node count) is the node to
+ * visit when box i is missed or its subtree is done.  A leaf holds the
+ * triangles node_first .. node_first + node_count - 1 of the mesh's range of
+ * `tri` (mesh_tri0[m] ..), which is in BVH order; tri_face gives each one's
+ * face id in the mesh file.  Traversal: i = 0; if box i is hit, ends at
+ * t >= 0 and is entered at t <= the best hit so far, test the leaf's triangles
+ * or descend (i + 1); else i = skip[i].  Boxes are expected padded outwards
+ * (mgs/scan/bvh.py) so that the result equals a sweep over every triangle. */
+#define MGS_SCAN_BOX 0
+#define MGS_SCAN_SPHERE 1
+#define MGS_SCAN_MESH 2
+typedef struct mgs_scan_scene {
+  int32_t ndraw, nmesh, nnode, ntri;
+  int32_t *draw_type;        /* ndraw: MGS_SCAN_* */
+  int32_t *draw_id;          /* ndraw: the segmentation id reported for a hit */
+  int32_t *draw_mesh;        /* ndraw: mesh index of a mesh instance (else ignored) */
+  double *draw_pos;          /* ndraw * 3: geom frame origin, world */
+  double *draw_rot;          /* ndraw * 9: geom frame axes (row-major, frame -> world) */
+  double *draw_size;         /* ndraw * 3: box half extents; sphere radius first */
+  int32_t *mesh_node0;       /* nmesh + 1 */
+  int32_t *mesh_tri0;        /* nmesh + 1 */
+  double *node_box;          /* nnode * 6: min xyz, max xyz (mesh frame) */
+  int32_t *node_skip;        /* nnode */
+  int32_t *node_first;       /* nnode */
+  int32_t *node_count;       /* nnode: 0 = inner node */
+  double *tri;               /* ntri * 9: v0 v1 v2 (mesh frame) */
+  int32_t *tri_face;         /* ntri */
+} mgs_scan_scene;
+
+/* One ray per pixel of nview cameras (cam_pos nview * 3; cam_rot nview * 9
+ * row-major, columns = the camera's x (right), y (down), z (forward) axes in
+ * the world): the ray of pixel (row r, column c) starts at cam_pos along
+ * cam_rot * ((c + 0.5 - cx) / fx, (r + 0.5 - cy) / fy, 1), so its parameter t
+ * is the planar depth.  The nearest hit is the lexicographic minimum of
+ * (t, drawable index, face id) over hits with t > 0: triangles two-sided
+ * (Moeller-Trumbore as mgs_antipodal_contacts), a sphere's smallest positive
+ * root, a box's entry or, from inside, its exit.  Outputs, nview * height *
+ * width each: out_depth (t, 0 on a miss), out_seg (draw_id, -1 on a miss),
+ * out_tri (face id, -1 for a box, a sphere or a miss), out_ntest (ray-triangle
+ * tests the pixel performed; may be NULL).  The scene's index arrays are
+ * checked (MGS_EINVAL) before anything is launched. */
+int mgs_scan_render(int device, const mgs_scan_scene* scene, int nview, const double* cam_pos,
+                    const double* cam_rot, int width, int height, double fx, double fy, double cx, double cy,
+                    double* out_depth, int32_t* out_seg, int32_t* out_tri, int32_t* out_ntest, double* kernel_ms);
+
+/* Points of depth images (depth, seg: nview * height * width; extrinsics
+ * nview * 16, row-major 4 x 4 camera -> world): per pixel (r, c) with depth z
+ * the camera-frame point ((c - cx) z / fx, (r - cy) z / fy, z) -- no half-pixel
+ * offset, as the reference -- through the extrinsic into out_points
+ * (n * 3).  out_keep = the pixel survives erode_iters 3 x 3 erosions of the
+ * mask seg != -1 (pixels outside the image count as set, cv2.erode's default
+ * border) and its point lies strictly inside region (lo xyz, hi xyz; NULL =
+ * the reference's (-0.25, -0.25, -0.01) .. (0.25, 0.25, 1.0)).  Compaction is
+ * the caller's. */
+int mgs_scan_points(int device, int nview, int width, int height, const double* depth, const int32_t* seg,
+                    const double* extrinsics, double fx, double fy, double cx, double cy, int erode_iters,
+                    const double* region, double* out_points, uint8_t* out_keep, double* kernel_ms);
+
 /* Duration (ms) of the last rollout kernel launch, measured with HIP events
  * on the launch stream (waits for it). */
 double mgs_last_kernel_ms(mgs_batch* batch);

@@ -11,6 +11,7 @@
 #include "mgs_launch.h"
 #include "mgs_aux.hip"
 #include "mgs_sampler.hip"
+#include "mgs_scan.hip"
 #include "mgs_contact.hip"
 
 #include <cstdlib>
@@ -1055,6 +1056,132 @@ int mgs_contact_optimize(int device, const mgs_kin_desc* kin, int n, const doubl
     HIPCHK(hipMemcpy(out_pos, oP, 3 * nn * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out_joints, oJ, nd * nn * sizeof(double), hipMemcpyDeviceToHost));
     if (out_loss) HIPCHK(hipMemcpy(out_loss, oL, nn * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return rc;
+}
+
+// ---------------------------------------------------------------------------
+// scene scan (csrc/mgs_scan.hip)
+}  // extern "C"
+namespace {
+// every index the scan kernel follows, checked on the host: "" or what is wrong
+const char* scan_scene_error(const mgs_scan_scene* s) {
+  if (s->ndraw < 0 || s->nmesh < 0 || s->nnode < 0 || s->ntri < 0) return "negative count";
+  if (s->ndraw > 0 && (!s->draw_type || !s->draw_id || !s->draw_mesh || !s->draw_pos || !s->draw_rot || !s->draw_size))
+    return "null drawable array";
+  if (s->nmesh > 0 && (!s->mesh_node0 || !s->mesh_tri0)) return "null mesh range array";
+  if (s->nnode > 0 && (!s->node_box || !s->node_skip || !s->node_first || !s->node_count)) return "null node array";
+  if (s->ntri > 0 && (!s->tri || !s->tri_face)) return "null triangle array";
+  for (int m = 0; m < s->nmesh; m++) {
+    const int n0 = s->mesh_node0[m], n1 = s->mesh_node0[m + 1], t0 = s->mesh_tri0[m], t1 = s->mesh_tri0[m + 1];
+    if (n0 < 0 || n1 < n0 || n1 > s->nnode || t0 < 0 || t1 < t0 || t1 > s->ntri) return "mesh range out of bounds";
+    for (int i = 0; i < n1 - n0; i++) {
+      const int g = n0 + i, cnt = s->node_count[g], first = s->node_first[g], skip = s->node_skip[g];
+      if (skip <= i || skip > n1 - n0) return "skip index not forward or out of range";
+      if (cnt < 0) return "negative leaf count";
+      if (cnt > 0 && (first < 0 || first > t1 - t0 - cnt)) return "leaf triangles out of range";
+      if (cnt == 0 && i + 1 >= n1 - n0) return "inner node without a child";
+    }
+  }
+  for (int d = 0; d < s->ndraw; d++) {
+    const int t = s->draw_type[d];
+    if (t != MGS_SCAN_BOX && t != MGS_SCAN_SPHERE && t != MGS_SCAN_MESH) return "unknown drawable type";
+    if (t == MGS_SCAN_MESH && (s->draw_mesh[d] < 0 || s->draw_mesh[d] >= s->nmesh)) return "mesh index out of range";
+  }
+  return "";
+}
+template <class T>
+T* scan_upload(DevBufs& b, const T* src, size_t n) {
+  T* d = b.get<T>(n);
+  if (d && n > 0 && hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) b.ok = false;
+  return d;
+}
+}  // namespace
+extern "C" {
+
+int mgs_scan_render(int device, const mgs_scan_scene* scene, int nview, const double* cam_pos,
+                    const double* cam_rot, int width, int height, double fx, double fy, double cx, double cy,
+                    double* out_depth, int32_t* out_seg, int32_t* out_tri, int32_t* out_ntest, double* kernel_ms) {
+  if (!scene) return fail(MGS_EINVAL, "mgs_scan_render: null scene%s");
+  if (nview < 0 || width < 0 || height < 0) return fail(MGS_EINVAL, "mgs_scan_render: negative size%s");
+  if (nview > 65535) return fail(MGS_EINVAL, "mgs_scan_render: at most 65535 views per call%s");
+  if (!(fx > 0.0) || !(fy > 0.0)) return fail(MGS_EINVAL, "mgs_scan_render: focal lengths must be positive%s");
+  const char* bad = scan_scene_error(scene);
+  if (bad[0]) return fail(MGS_EINVAL, "mgs_scan_render: scene: %s", bad);
+  const size_t n = (size_t)nview * (size_t)width * (size_t)height;
+  if (n > (size_t)1 << 30) return fail(MGS_EINVAL, "mgs_scan_render: more than 2^30 pixels%s");
+  if (n == 0) return MGS_OK;
+  if (!cam_pos || !cam_rot || !out_depth || !out_seg || !out_tri)
+    return fail(MGS_EINVAL, "mgs_scan_render: null argument%s");
+  HIPCHK(hipSetDevice(device));
+  DevBufs b;
+  const size_t nd = (size_t)scene->ndraw, nm = (size_t)scene->nmesh, nn = (size_t)scene->nnode, nt = (size_t)scene->ntri;
+  ScanDev S;
+  S.ndraw = scene->ndraw;
+  S.dtype = scan_upload(b, scene->draw_type, nd);
+  S.did = scan_upload(b, scene->draw_id, nd);
+  S.dmesh = scan_upload(b, scene->draw_mesh, nd);
+  S.dpos = scan_upload(b, scene->draw_pos, 3 * nd);
+  S.drot = scan_upload(b, scene->draw_rot, 9 * nd);
+  S.dsize = scan_upload(b, scene->draw_size, 3 * nd);
+  S.mnode0 = scan_upload(b, scene->mesh_node0, nm ? nm + 1 : 0);
+  S.mtri0 = scan_upload(b, scene->mesh_tri0, nm ? nm + 1 : 0);
+  S.nbox = scan_upload(b, scene->node_box, 6 * nn);
+  S.nskip = scan_upload(b, scene->node_skip, nn);
+  S.nfirst = scan_upload(b, scene->node_first, nn);
+  S.ncount = scan_upload(b, scene->node_count, nn);
+  S.tri = scan_upload(b, scene->tri, 9 * nt);
+  S.face = scan_upload(b, scene->tri_face, nt);
+  double* dP = scan_upload(b, cam_pos, 3 * (size_t)nview);
+  double* dR = scan_upload(b, cam_rot, 9 * (size_t)nview);
+  double* oD = b.get<double>(n);
+  int32_t* oS = b.get<int32_t>(n);
+  int32_t* oT = b.get<int32_t>(n);
+  int32_t* oN = b.get<int32_t>(n);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
+  EvTimer t;
+  hipLaunchKernelGGL(mgs_scan_kernel,
+                     dim3((width + MGS_SCAN_TILE - 1) / MGS_SCAN_TILE, (height + MGS_SCAN_TILE - 1) / MGS_SCAN_TILE, nview),
+                     dim3(MGS_SCAN_TILE * MGS_SCAN_TILE), 0, nullptr, S, dP, dR, width, height, fx, fy, cx, cy, oD, oS,
+                     oT, oN);
+  int rc = t.finish(kernel_ms);
+  if (rc == MGS_OK) {
+    HIPCHK(hipMemcpy(out_depth, oD, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_seg, oS, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_tri, oT, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (out_ntest) HIPCHK(hipMemcpy(out_ntest, oN, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  return rc;
+}
+
+int mgs_scan_points(int device, int nview, int width, int height, const double* depth, const int32_t* seg,
+                    const double* extrinsics, double fx, double fy, double cx, double cy, int erode_iters,
+                    const double* region, double* out_points, uint8_t* out_keep, double* kernel_ms) {
+  if (nview < 0 || width < 0 || height < 0) return fail(MGS_EINVAL, "mgs_scan_points: negative size%s");
+  if (erode_iters < 0 || erode_iters > 64) return fail(MGS_EINVAL, "mgs_scan_points: erode_iters must be 0 .. 64%s");
+  if (!(fx > 0.0) || !(fy > 0.0)) return fail(MGS_EINVAL, "mgs_scan_points: focal lengths must be positive%s");
+  const size_t n = (size_t)nview * (size_t)width * (size_t)height;
+  if (n > (size_t)1 << 30) return fail(MGS_EINVAL, "mgs_scan_points: more than 2^30 pixels%s");
+  if (n == 0) return MGS_OK;
+  if (!depth || !seg || !extrinsics || !out_points || !out_keep)
+    return fail(MGS_EINVAL, "mgs_scan_points: null argument%s");
+  static const double ref_region[6] = {-0.25, -0.25, -0.01, 0.25, 0.25, 1.0};
+  const double* rg = region ? region : ref_region;
+  HIPCHK(hipSetDevice(device));
+  DevBufs b;
+  double* dD = scan_upload(b, depth, n);
+  int32_t* dS = scan_upload(b, seg, n);
+  double* dE = scan_upload(b, extrinsics, 16 * (size_t)nview);
+  double* oP = b.get<double>(3 * n);
+  uint8_t* oK = b.get<uint8_t>(n);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
+  EvTimer t;
+  hipLaunchKernelGGL(mgs_scan_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, nview, width,
+                     height, dD, dS, dE, fx, fy, cx, cy, erode_iters, rg[0], rg[1], rg[2], rg[3], rg[4], rg[5], oP, oK);
+  int rc = t.finish(kernel_ms);
+  if (rc == MGS_OK) {
+    HIPCHK(hipMemcpy(out_points, oP, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_keep, oK, n * sizeof(uint8_t), hipMemcpyDeviceToHost));
   }
   return rc;
 }

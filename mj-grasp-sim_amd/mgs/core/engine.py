@@ -84,6 +84,10 @@ def load_library(wide: bool = False):
     L.mgs_contact_seeds.argtypes = [ctypes.c_int, P(c_d), ctypes.c_int, c_d, ctypes.c_uint64, ctypes.c_int, P(c_i),
                                     P(c_i), P(c_d)]
     L.mgs_contact_optimize.argtypes = [ctypes.c_int, P(abi.KinDesc), ctypes.c_int] + [P(c_d)] * 9
+    L.mgs_scan_render.argtypes = [ctypes.c_int, P(abi.ScanScene), ctypes.c_int, P(c_d), P(c_d), ctypes.c_int,
+                                  ctypes.c_int, c_d, c_d, c_d, c_d, P(c_d), P(c_i), P(c_i), P(c_i), P(c_d)]
+    L.mgs_scan_points.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(c_d), P(c_i), P(c_d),
+                                  c_d, c_d, c_d, c_d, ctypes.c_int, P(c_d), P(c_d), P(c_u8), P(c_d)]
     L.mgs_supports_nv.argtypes = [ctypes.c_int]
     L.mgs_supports_nv.restype = ctypes.c_int
     L.mgs_rollout_grid.argtypes = [vp, ctypes.c_int]
@@ -554,6 +558,55 @@ def contact_fps(points, k, device=0):
     _check(L.mgs_contact_fps(device, ptr(x, ctypes.c_double), len(x), int(k), ptr(out, ctypes.c_int32),
                              ctypes.byref(ms)), "mgs_contact_fps", L)
     return out, ms.value
+
+
+def scan_render(scene_arrays, cam_pos, cam_rot, width, height, fx, fy, cx, cy, device=0):
+    """ray-cast depth / segmentation images on the GPU (mgs_scan_render).
+    scene_arrays: mgs.scan.scene.ScanScene.arrays(); cam_pos (nview, 3), cam_rot
+    (nview, 3, 3) with OpenCV axes.  Returns dict(depth f64, seg, tri, ntest
+    (nview, height, width), kernel_ms)."""
+    from mgs.scan.scene import pack_scene
+    L = _device_lib(device)
+    scene, keep = pack_scene(scene_arrays)
+    cp = np.ascontiguousarray(cam_pos, np.float64).reshape(-1, 3)
+    cr = np.ascontiguousarray(cam_rot, np.float64).reshape(-1, 3, 3)
+    if len(cp) != len(cr):
+        raise ValueError("one rotation per camera position")
+    shape = (len(cp), int(height), int(width))
+    if min(shape) < 0:
+        raise ValueError("negative image size")
+    depth = np.zeros(shape)
+    seg, tri, ntest = (np.zeros(shape, np.int32) for _ in range(3))
+    ms = ctypes.c_double(0.0)
+    _check(L.mgs_scan_render(device, ctypes.byref(scene), len(cp), ptr(cp, ctypes.c_double),
+                             ptr(cr, ctypes.c_double), int(width), int(height), float(fx), float(fy), float(cx),
+                             float(cy), ptr(depth, ctypes.c_double), ptr(seg, ctypes.c_int32),
+                             ptr(tri, ctypes.c_int32), ptr(ntest, ctypes.c_int32), ctypes.byref(ms)),
+           "mgs_scan_render", L)
+    del keep
+    return dict(depth=depth, seg=seg, tri=tri, ntest=ntest, kernel_ms=ms.value)
+
+
+def scan_points(depth, seg, extrinsics, fx, fy, cx, cy, erode_iters=5, region=None, device=0):
+    """eroded mask, back-projection, extrinsic and region crop of depth images
+    on the GPU (mgs_scan_points): (points (nview, H, W, 3), keep bool (nview, H,
+    W), kernel ms).  region: (lo xyz, hi xyz), default the reference's crop."""
+    L = _device_lib(device)
+    d = np.ascontiguousarray(depth, np.float64)
+    s = np.ascontiguousarray(seg, np.int32)
+    e = np.ascontiguousarray(extrinsics, np.float64).reshape(-1, 4, 4)
+    if d.ndim != 3 or s.shape != d.shape or len(e) != len(d):
+        raise ValueError("depth and seg are (nview, height, width); one extrinsic per view")
+    nview, h, w = d.shape
+    pts = np.zeros((nview, h, w, 3))
+    keep = np.zeros((nview, h, w), np.uint8)
+    rg = None if region is None else np.ascontiguousarray(region, np.float64).reshape(6)
+    ms = ctypes.c_double(0.0)
+    _check(L.mgs_scan_points(device, nview, w, h, ptr(d, ctypes.c_double), ptr(s, ctypes.c_int32),
+                             ptr(e, ctypes.c_double), float(fx), float(fy), float(cx), float(cy), int(erode_iters),
+                             None if rg is None else ptr(rg, ctypes.c_double), ptr(pts, ctypes.c_double),
+                             ptr(keep, ctypes.c_uint8), ctypes.byref(ms)), "mgs_scan_points", L)
+    return pts, keep.astype(bool), ms.value
 
 
 def contact_seeds(seeds, radius, rng_seed, ntip, device=0):

@@ -25,6 +25,7 @@ bodies at their state pose; the state vector keeps their slots.
 """
 from __future__ import annotations
 
+import os
 import xml.etree.ElementTree as Et
 from copy import deepcopy
 from typing import List, Optional
@@ -80,6 +81,14 @@ XML = r"""
 
 CAMERA_QPOS0 = np.array([0.0, 0.0, -1.0, 1.0, 0.0, 0.0, 0.0])   # :46
 
+# what the scan draws of the XML above: the table box, the base_origin marker
+# (the camera's target), and MuJoCo's default camera field of view (degrees)
+SCAN_TABLE_POS = np.array([0.0, 0.0, -0.02])
+SCAN_TABLE_SIZE = np.array([10.0, 10.0, 0.02])
+SCAN_TARGET = np.array([0.0, 0.0, -0.025])
+SCAN_ORIGIN_RADIUS = 0.01
+SCAN_FOVY = 45.0
+
 
 def _frozen_object_xml(xml_bytes: bytes, qpos7) -> bytes:
     """an object include with its free joint removed, its geoms contact-free and
@@ -127,6 +136,13 @@ class ClutterTableEnv:
         self._model_key = None
         self._model = None
         self._engines = {}
+        # scan (render-only): image size of the intrinsics, camera (pos, MuJoCo
+        # frame), mesh files read so far, the scene dict's table colour
+        self.scan_width = self.scan_height = 480
+        self._scan_cam = None
+        self._scan_meshes = {}
+        self.table_rgba = None
+        self.last_scan = None
 
     def _check_kernel(self, nv):
         """the kernels hold up to 128 dofs (lanes over dofs: one per lane up to
@@ -306,6 +322,8 @@ class ClutterTableEnv:
         state = {"geom_conaffinity": contype.copy(), "geom_contype": contype, "geom_rgba": np.ones((ng, 4)),
                  "body_gravcomp": gravcomp, "state": self.get_state(),
                  "removed_objects": sorted(self.removed)}
+        if self.table_rgba is not None:      # the scan's table colour (scan_colors)
+            state["table_rgba"] = np.array(self.table_rgba, np.float64)
         return {"gripper": deepcopy(self.gripper), "objects": deepcopy(self.objects), "env_state": state}
 
     @classmethod
@@ -322,6 +340,8 @@ class ClutterTableEnv:
                     removed.add(o.name)
         env.removed = removed
         env._model_key = None
+        if state.get("table_rgba") is not None:
+            env.table_rgba = np.asarray(state["table_rgba"], np.float64)
         return env
 
     # -- host bookkeeping ------------------------------------------------------
@@ -582,3 +602,113 @@ class ClutterTableEnv:
         ok, _, st = self.is_stable_states(self._state)
         self._state = st[0]
         return bool(ok[0])
+
+    # -- scan (MjScanEnv, env/base.py:28-126; update_camera_settings :224-235) ---
+    # Geometry only: depth, geom segmentation, flat per-geom colours (DESIGN
+    # "Scene scan").  The camera is render-only state of this object; the camera
+    # body's slots of the integration state are left alone.
+    @property
+    def scan_geom_names(self) -> List[str]:
+        """what a segmentation id indexes: the table, the origin marker, then
+        every object's visual mesh geom under the object's name"""
+        return ["geom:table", "geom:base_origin"] + list(self.object_names)
+
+    def scan_scene(self):
+        """the drawables of MuJoCo's default options for this env's state: the
+        table box, the base_origin sphere and the visual mesh (group 2) of every
+        object not removed, at the body pose of the integration state (the mesh
+        file's own vertices: MuJoCo's recentring moves frame and vertices
+        oppositely).  Walls (alpha 0), the camera's own geom (behind the near
+        plane), collision meshes (group 3) and the gripper (no visual geoms in
+        this build's models) are not drawn."""
+        from mgs.core.mjcf import load_mesh_bytes
+        from mgs.scan.scene import ScanScene, quat_to_mat
+        sc = ScanScene()
+        sc.add_box(0, SCAN_TABLE_POS, None, SCAN_TABLE_SIZE)
+        sc.add_sphere(1, SCAN_TARGET, SCAN_ORIGIN_RADIUS)
+        q = self.split_state(self._state)["qpos"]
+        for k, (o, (name, qs, _)) in enumerate(zip(self.objects, self._obj_slices())):
+            if name in self.removed:
+                continue
+            path = os.path.join(o.asset_dir, o.info()["original_file"])
+            if path not in self._scan_meshes:
+                with open(path, "rb") as f:
+                    self._scan_meshes[path] = load_mesh_bytes(f.read(), path)
+            v, f = self._scan_meshes[path]
+            quat = q[qs][3:7] / np.linalg.norm(q[qs][3:7])
+            sc.add_mesh(2 + k, q[qs][:3], quat_to_mat(quat), v, f, key=path)
+        return sc
+
+    def update_camera_settings(self, num_images, i):
+        """view i of num_images: the Fibonacci point lifted into the upper
+        hemisphere (z = |z| + 0.01), looking at base_origin by MuJoCo's
+        `targetbody` rule (restated: mgs.scan.scene.look_at_frame)"""
+        from mgs.scan.scene import look_at_frame
+        from mgs.util.camera import fibonacci_sphere
+        pos = fibonacci_sphere(total_num=num_images, i=i)
+        pos[2] = np.abs(pos[2]) + 0.01
+        self._scan_cam = (pos, look_at_frame(pos, SCAN_TARGET))
+
+    def get_camera_extrinsics(self) -> np.ndarray:
+        """camera -> world with OpenCV axes (x right, y down, z forward): MuJoCo's
+        camera frame [x, y, z | pos] turned by 180 degrees about x, as the
+        reference's scan returns it (env/base.py:114-116)"""
+        if self._scan_cam is None:
+            from mgs.scan.scene import look_at_frame
+            self._scan_cam = (CAMERA_QPOS0[:3].copy(), look_at_frame(CAMERA_QPOS0[:3], SCAN_TARGET))
+        pos, R = self._scan_cam
+        E = np.eye(4)
+        E[:3, 0], E[:3, 1], E[:3, 2], E[:3, 3] = R[:, 0], -R[:, 1], -R[:, 2], pos
+        return E
+
+    def get_camera_intrinsics(self) -> np.ndarray:
+        """the reference's matrix (env/base.py:44-59), quirk included: fy is the
+        pinhole focal length of fovy, fx that of a horizontal angle computed
+        from fovy / 2 (fx = (H / 2) / tan(fovy pi / 720) for W = H), about
+        2.08 fy.  Downstream code consumes these numbers."""
+        w, h = self.scan_width, self.scan_height
+        fy = (h / 2) / np.tan(SCAN_FOVY * np.pi / 360)
+        fx = (w / 2) / (w * 0.5 / (h * 0.5 / np.tan(SCAN_FOVY * np.pi / 720)))
+        return np.array([[fx, 0, w / 2], [0, fy, h / 2], [0, 0, 1]])
+
+    def get_render_intrinsics(self) -> np.ndarray:
+        """what the images are rendered with (MuJoCo's: square pixels, f = fy on
+        both axes); the ray of pixel (r, c) passes through its centre,
+        ((c + 0.5 - cx) / f, (r + 0.5 - cy) / f, 1) in the camera frame"""
+        w, h = self.scan_width, self.scan_height
+        f = (h / 2) / np.tan(SCAN_FOVY * np.pi / 360)
+        return np.array([[f, 0, w / 2], [0, f, h / 2], [0, 0, 1]])
+
+    def scan(self, num_images=1, width=480, height=480):
+        """env/base.py:77-126 on the GPU (mgs_scan_render): (rgbd (N, H, W, 4)
+        float32 -- flat geom colour in [0, 1] and planar depth, 0 where nothing
+        is hit --, extrinsics (N, 4, 4), image_masks (N, H, W) bool: the hit mask
+        eroded 5 times, segmentation (N, H, W) int32: index into
+        scan_geom_names, -1 = nothing).  `last_scan` keeps the f64 depth, the hit
+        face ids, the per-pixel triangle-test counts and the kernel time."""
+        from mgs.core.engine import scan_render
+        from mgs.scan.scene import erode_mask
+        self.scan_width, self.scan_height = int(width), int(height)
+        extr = []
+        for i in range(num_images):
+            self.update_camera_settings(num_images, i)
+            extr.append(self.get_camera_extrinsics())
+        extr = np.stack(extr, axis=0) if extr else np.zeros((0, 4, 4))
+        K = self.get_render_intrinsics()
+        res = scan_render(self.scan_scene().arrays(), extr[:, :3, 3], extr[:, :3, :3], width, height,
+                          K[0, 0], K[1, 1], K[0, 2], K[1, 2], device=self.device)
+        seg = res["seg"]
+        colors = np.concatenate([self.scan_colors(), np.zeros((1, 3))]).astype(np.float32)   # [-1]: a miss
+        rgbd = np.concatenate([colors[seg], res["depth"].astype(np.float32)[..., None]], axis=-1)
+        self.last_scan = res
+        return rgbd, extr, erode_mask(seg != -1, 5), seg
+
+    def scan_colors(self) -> np.ndarray:
+        """flat colour per entry of scan_geom_names: the table's from the scene
+        dict where it has one (`table_rgba`), else 0.5 grey; the origin marker
+        red as in the reference's model; objects 0.5 grey"""
+        c = np.full((len(self.scan_geom_names), 3), 0.5)
+        if self.table_rgba is not None:
+            c[0] = np.asarray(self.table_rgba, np.float64)[:3]
+        c[1] = [1.0, 0.0, 0.0]
+        return c
