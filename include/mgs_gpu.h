@@ -726,6 +726,79 @@ int mgs_scan_points(int device, int nview, int width, int height, const double* 
                     const double* extrinsics, double fx, double fy, double cx, double cy, int erode_iters,
                     const double* region, double* out_points, uint8_t* out_keep, double* kernel_ms);
 
+/* ---------------------------------------------------------------------------
+ * Scene cloud (csrc/mgs_cloud.hip): what mgs/cli/render_scene_processed does
+ * between the depth images and scene_pcd.npz, on the device.  Additive entries
+ * (the ABI version stays).  Host pointers, synchronous on `device`; every
+ * argument is checked before anything is launched or written. */
+
+/* largest dense grid (cells) the voxel stage builds: 2^28 cells, 1 GiB of
+ * counters; the reference region at 2 mm is 31.6 M cells */
+#define MGS_CLOUD_MAX_CELLS 268435456
+/* most cells of the pick's bucket grid; the bucket side is doubled until the
+ * grid over the points' bounding box has no more */
+#define MGS_CLOUD_FPS_MAX_CELLS 16777216
+
+/* mgs.util.img_proc.voxel_downsample_pcd(points[keep], features[keep],
+ * voxel_size), bit for bit: points n * 3 f64, keep n (NULL = all), features
+ * n * nfeat float32 (NULL with nfeat 0).  The grid is anchored at the
+ * component-wise minimum of the kept points; a point's cell per axis is numpy's
+ * float floor_divide of (p - min) by voxel_size (mod = fmod(a, b),
+ * div = (a - mod) / b, cell 0 if div == 0, else floor(div), plus 1 if
+ * div - floor(div) > 0.5); voxels come in ascending (x, y, z) cell; a voxel's
+ * position is the f64 sum of its points in ascending index (from +0.0) over
+ * (double)count, its features the float32 sums in the same order, divided in
+ * f64 and rounded to float32.  Outputs: out_points (cap * 3), out_features
+ * (cap * nfeat; may be NULL with nfeat 0), out_count (cap; may be NULL), of
+ * which *out_nvox rows are written.
+ * MGS_EINVAL: negative n / nfeat / cap, a voxel_size that is not positive and
+ * finite, a kept point that is not finite, a grid whose raveled index
+ * overflows int64 (numpy raises there).  MGS_ECAPACITY: more voxels than cap
+ * (*out_nvox = the count, nothing else written), or a grid of more than
+ * MGS_CLOUD_MAX_CELLS cells (*out_nvox = -1). */
+int mgs_scan_voxels(int device, int n, const double* points, const uint8_t* keep, int nfeat, const float* features,
+                    double voxel_size, int cap, double* out_points, float* out_features, int32_t* out_count,
+                    int32_t* out_nvox, double* kernel_ms);
+
+/* The indices mgs_contact_fps returns (out_idx[0] = 0, d = (d0 d0 + d1 d1) +
+ * d2 d2, running minimum updated on d < c, next = the maximum, lowest index
+ * among equals), computed with spatial pruning.  Buckets are the occupied cells
+ * of a grid anchored at the points' minimum, cell = floor((p - min) / side) per
+ * axis, side = bucket_size doubled until the grid over the bounding box has at
+ * most MGS_CLOUD_FPS_MAX_CELLS cells.  Per pick p a bucket with box [lo, hi] is
+ * skipped when lb = (e0 e0 + e1 e1) + e2 e2, e_k = max(lo_k - p_k, p_k - hi_k,
+ * 0), is >= the bucket's current maximum of running minima: rounding is
+ * monotone, so every point of it has d >= lb and cannot change.  out_nevals
+ * (may be NULL) = point distances computed; a sweep computes n (k - 1).
+ * Argument rules as mgs_contact_fps; in addition bucket_size must be positive
+ * and finite and every point finite (MGS_EINVAL). */
+int mgs_scan_fps(int device, const double* points, int n, int k, double bucket_size, int32_t* out_idx,
+                 int64_t* out_nevals, double* kernel_ms);
+
+/* render -> points -> voxels -> pick with every intermediate on the device:
+ *  1. depth and segmentation as mgs_scan_render (fx, fy, cx, cy);
+ *  2. the depth rounded to float32 and widened again;
+ *  3. points and keep as mgs_scan_points (extrinsics, pfx, pfy, pcx, pcy,
+ *     erode_iters, region or NULL);
+ *  4. the kept pixels compacted in (view, row, column) order, each with the
+ *     float32 row colors[draw_id] (colors: ncolor * 3; every draw_id of the
+ *     scene must lie in [0, ncolor));
+ *  5. the voxel grid of mgs_scan_voxels;
+ *  6. with at least num_points voxels: the pick of mgs_scan_fps among the
+ *     float32-rounded voxel positions (widened to f64), bucket_size =
+ *     8 voxel_size, and the picked voxels in pick order; else every voxel in
+ *     voxel order;
+ *  7. out_points / out_colors (num_points * 3 float32): *out_n rows written,
+ *     the rest untouched.
+ * out_stats (8, may be NULL): kept points, voxels, pick distance evaluations,
+ * grid cells, rows written, pixels, 0, 0.  stage_ms (4, may be NULL): render,
+ * points + compaction, voxels, pick (HIP events).  Errors as the entries above. */
+int mgs_scan_cloud(int device, const mgs_scan_scene* scene, int nview, const double* cam_pos, const double* cam_rot,
+                   int width, int height, double fx, double fy, double cx, double cy, const double* extrinsics,
+                   double pfx, double pfy, double pcx, double pcy, int erode_iters, const double* region,
+                   const float* colors, int ncolor, double voxel_size, int num_points, float* out_points,
+                   float* out_colors, int32_t* out_n, int64_t* out_stats, double* stage_ms);
+
 /* Duration (ms) of the last rollout kernel launch, measured with HIP events
  * on the launch stream (waits for it). */
 double mgs_last_kernel_ms(mgs_batch* batch);

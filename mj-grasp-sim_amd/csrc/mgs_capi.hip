@@ -13,6 +13,7 @@
 #include "mgs_sampler.hip"
 #include "mgs_scan.hip"
 #include "mgs_contact.hip"
+#include "mgs_cloud.hip"
 
 #include <cstdlib>
 
@@ -1096,6 +1097,27 @@ T* scan_upload(DevBufs& b, const T* src, size_t n) {
   if (d && n > 0 && hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) b.ok = false;
   return d;
 }
+// a checked scene's arrays on the device
+ScanDev scan_upload_scene(DevBufs& b, const mgs_scan_scene* scene) {
+  const size_t nd = (size_t)scene->ndraw, nm = (size_t)scene->nmesh, nn = (size_t)scene->nnode, nt = (size_t)scene->ntri;
+  ScanDev S;
+  S.ndraw = scene->ndraw;
+  S.dtype = scan_upload(b, scene->draw_type, nd);
+  S.did = scan_upload(b, scene->draw_id, nd);
+  S.dmesh = scan_upload(b, scene->draw_mesh, nd);
+  S.dpos = scan_upload(b, scene->draw_pos, 3 * nd);
+  S.drot = scan_upload(b, scene->draw_rot, 9 * nd);
+  S.dsize = scan_upload(b, scene->draw_size, 3 * nd);
+  S.mnode0 = scan_upload(b, scene->mesh_node0, nm ? nm + 1 : 0);
+  S.mtri0 = scan_upload(b, scene->mesh_tri0, nm ? nm + 1 : 0);
+  S.nbox = scan_upload(b, scene->node_box, 6 * nn);
+  S.nskip = scan_upload(b, scene->node_skip, nn);
+  S.nfirst = scan_upload(b, scene->node_first, nn);
+  S.ncount = scan_upload(b, scene->node_count, nn);
+  S.tri = scan_upload(b, scene->tri, 9 * nt);
+  S.face = scan_upload(b, scene->tri_face, nt);
+  return S;
+}
 }  // namespace
 extern "C" {
 
@@ -1115,23 +1137,7 @@ int mgs_scan_render(int device, const mgs_scan_scene* scene, int nview, const do
     return fail(MGS_EINVAL, "mgs_scan_render: null argument%s");
   HIPCHK(hipSetDevice(device));
   DevBufs b;
-  const size_t nd = (size_t)scene->ndraw, nm = (size_t)scene->nmesh, nn = (size_t)scene->nnode, nt = (size_t)scene->ntri;
-  ScanDev S;
-  S.ndraw = scene->ndraw;
-  S.dtype = scan_upload(b, scene->draw_type, nd);
-  S.did = scan_upload(b, scene->draw_id, nd);
-  S.dmesh = scan_upload(b, scene->draw_mesh, nd);
-  S.dpos = scan_upload(b, scene->draw_pos, 3 * nd);
-  S.drot = scan_upload(b, scene->draw_rot, 9 * nd);
-  S.dsize = scan_upload(b, scene->draw_size, 3 * nd);
-  S.mnode0 = scan_upload(b, scene->mesh_node0, nm ? nm + 1 : 0);
-  S.mtri0 = scan_upload(b, scene->mesh_tri0, nm ? nm + 1 : 0);
-  S.nbox = scan_upload(b, scene->node_box, 6 * nn);
-  S.nskip = scan_upload(b, scene->node_skip, nn);
-  S.nfirst = scan_upload(b, scene->node_first, nn);
-  S.ncount = scan_upload(b, scene->node_count, nn);
-  S.tri = scan_upload(b, scene->tri, 9 * nt);
-  S.face = scan_upload(b, scene->tri_face, nt);
+  ScanDev S = scan_upload_scene(b, scene);
   double* dP = scan_upload(b, cam_pos, 3 * (size_t)nview);
   double* dR = scan_upload(b, cam_rot, 9 * (size_t)nview);
   double* oD = b.get<double>(n);
@@ -1184,6 +1190,363 @@ int mgs_scan_points(int device, int nview, int width, int height, const double* 
     HIPCHK(hipMemcpy(out_keep, oK, n * sizeof(uint8_t), hipMemcpyDeviceToHost));
   }
   return rc;
+}
+
+// ---------------------------------------------------------------------------
+// scene cloud (csrc/mgs_cloud.hip)
+}  // extern "C"
+namespace {
+struct CloudVox {      // what the voxel stage leaves on the device (buffers owned by the caller's DevBufs)
+  uint32_t npts = 0, nvox = 0;
+  int64_t ncell = 0;
+  double* vpts = nullptr;
+  float* vfeat = nullptr;
+  int32_t* vcnt = nullptr;
+};
+
+size_t cloud_blocks(size_t n) { return (n + MGS_CLOUD_CHUNK - 1) / MGS_CLOUD_CHUNK; }
+
+// min / max / non-finite flag / kept count of x (n * 3) under keep (or NULL),
+// and the exclusive scan of the per-block kept counts in *sums
+int cloud_bounds(DevBufs& b, const double* dX, const uint8_t* dK, size_t n, cloud_u64** sums, CloudHdr* h) {
+  const size_t nb = cloud_blocks(n);
+  *sums = b.get<cloud_u64>(nb);
+  double* blo = b.get<double>(3 * nb);
+  double* bhi = b.get<double>(3 * nb);
+  int32_t* bbad = b.get<int32_t>(nb);
+  CloudHdr* dH = b.get<CloudHdr>(1);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
+  hipLaunchKernelGGL(cloud_flag_kernel, dim3((unsigned)nb), dim3(MGS_CLOUD_BLOCK), 0, nullptr, dX, dK, n, *sums, blo,
+                     bhi, bbad);
+  hipLaunchKernelGGL(cloud_scan_sums_kernel, dim3(1), dim3(MGS_CLOUD_BLOCK), 0, nullptr, *sums, nb, blo, bhi, bbad, dH);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(h, dH, sizeof(CloudHdr), hipMemcpyDeviceToHost));
+  return MGS_OK;
+}
+
+// counted grid (ncell) and the points' cells (npts) -> *start (occupied + 1:
+// first slot of every occupied cell in ascending cell, then npts), *slot_idx
+// (npts: point per slot, unordered inside a cell), *nocc.  cap >= 0: more
+// occupied cells than cap is MGS_ECAPACITY with *nocc set.
+int cloud_slots(DevBufs& b, uint32_t* grid, size_t ncell, const uint32_t* pcell, uint32_t npts, int64_t cap,
+                uint32_t** start, uint32_t** slot_idx, uint32_t* nocc) {
+  const size_t nb = cloud_blocks(ncell);
+  cloud_u64* sums = b.get<cloud_u64>(nb);
+  CloudHdr* dH = b.get<CloudHdr>(1);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
+  hipLaunchKernelGGL(cloud_cell_sums_kernel, dim3((unsigned)nb), dim3(MGS_CLOUD_BLOCK), 0, nullptr, grid, ncell, sums);
+  hipLaunchKernelGGL(cloud_scan_sums_kernel, dim3(1), dim3(MGS_CLOUD_BLOCK), 0, nullptr, sums, nb,
+                     (const double*)nullptr, (const double*)nullptr, (const int32_t*)nullptr, dH);
+  HIPCHK(hipGetLastError());
+  CloudHdr h;
+  HIPCHK(hipMemcpy(&h, dH, sizeof(cloud_u64), hipMemcpyDeviceToHost));
+  *nocc = (uint32_t)(h.total >> 32);
+  if ((uint32_t)h.total != npts || *nocc > npts) return fail(MGS_EHIP, "cloud grid: the cell counts do not add up%s");
+  if (cap >= 0 && (int64_t)*nocc > cap) return MGS_ECAPACITY;
+  *start = b.get<uint32_t>((size_t)*nocc + 1);
+  *slot_idx = b.get<uint32_t>(npts);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
+  hipLaunchKernelGGL(cloud_cell_offsets_kernel, dim3((unsigned)nb), dim3(MGS_CLOUD_BLOCK), 0, nullptr, grid, ncell, sums,
+                     *start, *nocc, npts);
+  hipLaunchKernelGGL(cloud_scatter_kernel, dim3((npts + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK), dim3(MGS_CLOUD_BLOCK),
+                     0, nullptr, pcell, npts, grid, *slot_idx);
+  HIPCHK(hipGetLastError());
+  return MGS_OK;
+}
+
+// the voxel stage on device arrays: dX (n * 3), dK (n or NULL), features dF
+// (n * nfeat) or, with dSeg, the rows dCol[dSeg] (nfeat 3).  `mid` (or NULL)
+// is recorded behind the compaction.  cap as cloud_slots.
+int cloud_voxels_dev(DevBufs& b, const double* dX, const uint8_t* dK, size_t n, const float* dF, int nfeat,
+                     const int32_t* dSeg, const float* dCol, int ncolor, double voxel_size, int64_t cap, CloudVox* V,
+                     hipEvent_t mid) {
+  *V = CloudVox();
+  int rc = MGS_OK;
+  cloud_u64* sums = nullptr;
+  CloudHdr h;
+  if (n > 0) rc = cloud_bounds(b, dX, dK, n, &sums, &h);
+  if (rc != MGS_OK || n == 0 || h.total == 0) {
+    if (mid) hipEventRecord(mid, nullptr);
+    return rc;
+  }
+  if (h.bad) return fail(MGS_EINVAL, "cloud voxels: a kept point is not finite%s");
+  CloudGrid G;
+  int64_t ncell = 1;
+  for (int k = 0; k < 3; k++) {
+    const double f = cloud_floor_divide(h.hi[k] - h.lo[k], voxel_size);
+    if (!(f < 4.0e18)) return fail(MGS_EINVAL, "cloud voxels: the grid's raveled index overflows int64%s");
+    G.lo[k] = h.lo[k];
+    G.dim[k] = (int64_t)f + 1;
+    if (__builtin_mul_overflow(ncell, G.dim[k], &ncell))
+      return fail(MGS_EINVAL, "cloud voxels: the grid's raveled index overflows int64%s");
+  }
+  G.side = voxel_size;
+  V->ncell = ncell;
+  if (ncell > (int64_t)MGS_CLOUD_MAX_CELLS) {
+    V->nvox = 0xffffffffu;
+    return fail(MGS_ECAPACITY, "cloud voxels: the grid has more than MGS_CLOUD_MAX_CELLS cells%s");
+  }
+  const uint32_t m = (uint32_t)h.total;
+  V->npts = m;
+  double* cpts = b.get<double>(3 * (size_t)m);
+  float* cfeat = b.get<float>((size_t)nfeat * m);
+  uint32_t* pcell = b.get<uint32_t>(m);
+  uint32_t* grid = b.get<uint32_t>((size_t)ncell);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
+  HIPCHK(hipMemsetAsync(grid, 0, (size_t)ncell * sizeof(uint32_t), nullptr));
+  hipLaunchKernelGGL(cloud_compact_kernel, dim3((unsigned)cloud_blocks(n)), dim3(MGS_CLOUD_BLOCK), 0, nullptr, dX, dK, n,
+                     sums, dF, nfeat, dSeg, dCol, ncolor, G, cpts, cfeat, pcell, grid);
+  if (mid) hipEventRecord(mid, nullptr);
+  uint32_t *start = nullptr, *slot_idx = nullptr;
+  rc = cloud_slots(b, grid, (size_t)ncell, pcell, m, cap, &start, &slot_idx, &V->nvox);
+  if (rc != MGS_OK) return rc == MGS_ECAPACITY ? fail(rc, "cloud voxels: more voxels than the outputs hold%s") : rc;
+  V->vpts = b.get<double>(3 * (size_t)V->nvox);
+  V->vfeat = b.get<float>((size_t)nfeat * V->nvox);
+  V->vcnt = b.get<int32_t>(V->nvox);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
+  hipLaunchKernelGGL(cloud_voxel_kernel, dim3((V->nvox + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK), dim3(MGS_CLOUD_BLOCK),
+                     0, nullptr, start, V->nvox, slot_idx, cpts, cfeat, nfeat, V->vpts, V->vfeat, V->vcnt);
+  HIPCHK(hipGetLastError());
+  return MGS_OK;
+}
+
+// the pick on device arrays: dX (n * 3, finite), 1 <= k <= n; dOut (k), dEv (1)
+int cloud_fps_dev(DevBufs& b, const double* dX, int n, int k, double bucket_size, int32_t* dOut, cloud_u64* dEv) {
+  cloud_u64* sums = nullptr;
+  CloudHdr h;
+  int rc = cloud_bounds(b, dX, nullptr, (size_t)n, &sums, &h);
+  if (rc != MGS_OK) return rc;
+  if (h.bad) return fail(MGS_EINVAL, "cloud pick: a point is not finite%s");
+  double ext[3];
+  for (int a = 0; a < 3; a++) {
+    ext[a] = h.hi[a] - h.lo[a];
+    if (!(ext[a] <= 1.7976931348623157e308)) return fail(MGS_EINVAL, "cloud pick: the points' extent is not finite%s");
+  }
+  CloudGrid G;
+  double side = bucket_size, d[3];
+  for (;;) {
+    for (int a = 0; a < 3; a++) d[a] = floor(ext[a] / side) + 1.0;
+    if (d[0] * d[1] * d[2] <= (double)MGS_CLOUD_FPS_MAX_CELLS) break;
+    side = side * 2.0;
+  }
+  for (int a = 0; a < 3; a++) { G.lo[a] = h.lo[a]; G.dim[a] = (int64_t)d[a]; }
+  G.side = side;
+  const size_t ncell = (size_t)(G.dim[0] * G.dim[1] * G.dim[2]);
+  uint32_t* pcell = b.get<uint32_t>((size_t)n);
+  uint32_t* grid = b.get<uint32_t>(ncell);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
+  HIPCHK(hipMemsetAsync(grid, 0, ncell * sizeof(uint32_t), nullptr));
+  const unsigned pb = ((unsigned)n + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK;
+  hipLaunchKernelGGL(cloud_fps_cell_kernel, dim3(pb), dim3(MGS_CLOUD_BLOCK), 0, nullptr, dX, (uint32_t)n, G, pcell, grid);
+  uint32_t *start = nullptr, *slot_idx = nullptr, nbkt = 0;
+  rc = cloud_slots(b, grid, ncell, pcell, (uint32_t)n, -1, &start, &slot_idx, &nbkt);
+  if (rc != MGS_OK) return rc;
+  double* bx = b.get<double>(3 * (size_t)n);
+  double* bdist = b.get<double>((size_t)n);
+  double* bbox = b.get<double>(6 * (size_t)nbkt);
+  double* bmax = b.get<double>(nbkt);
+  int32_t* bidx = b.get<int32_t>(nbkt);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
+  hipLaunchKernelGGL(cloud_fps_gather_kernel, dim3(pb), dim3(MGS_CLOUD_BLOCK), 0, nullptr, dX, (uint32_t)n, slot_idx, bx,
+                     bdist);
+  hipLaunchKernelGGL(cloud_fps_box_kernel, dim3((nbkt + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK), dim3(MGS_CLOUD_BLOCK), 0,
+                     nullptr, start, nbkt, slot_idx, bx, bbox, bmax, bidx);
+  hipLaunchKernelGGL(mgs_cloud_fps_kernel, dim3(1), dim3(MGS_CLOUD_FPS_THREADS), 0, nullptr, dX, bx, slot_idx, bdist,
+                     start, bbox, bmax, bidx, (int)nbkt, k, dOut, dEv);
+  HIPCHK(hipGetLastError());
+  return MGS_OK;
+}
+
+bool cloud_size_ok(double v) { return v > 0.0 && v <= 1.7976931348623157e308; }
+
+struct CloudEvents {
+  hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  CloudEvents() { for (auto& x : e) hipEventCreate(&x); }
+  ~CloudEvents() { for (auto& x : e) hipEventDestroy(x); }
+};
+}  // namespace
+extern "C" {
+
+int mgs_scan_voxels(int device, int n, const double* points, const uint8_t* keep, int nfeat, const float* features,
+                    double voxel_size, int cap, double* out_points, float* out_features, int32_t* out_count,
+                    int32_t* out_nvox, double* kernel_ms) {
+  if (n < 0 || nfeat < 0 || cap < 0) return fail(MGS_EINVAL, "mgs_scan_voxels: negative size%s");
+  if (n > (1 << 30)) return fail(MGS_EINVAL, "mgs_scan_voxels: more than 2^30 points%s");
+  if (!cloud_size_ok(voxel_size)) return fail(MGS_EINVAL, "mgs_scan_voxels: voxel_size must be positive and finite%s");
+  if (!out_nvox || (n > 0 && !points) || (n > 0 && nfeat > 0 && !features) ||
+      (cap > 0 && (!out_points || (nfeat > 0 && !out_features))))
+    return fail(MGS_EINVAL, "mgs_scan_voxels: null argument%s");
+  for (size_t j = 0; j < (size_t)n; j++) {
+    if (keep && !keep[j]) continue;
+    for (int a = 0; a < 3; a++)
+      if (!(fabs(points[3 * j + a]) <= 1.7976931348623157e308))
+        return fail(MGS_EINVAL, "mgs_scan_voxels: a kept point is not finite%s");
+  }
+  if (n == 0) { *out_nvox = 0; return MGS_OK; }
+  HIPCHK(hipSetDevice(device));
+  DevBufs b;
+  const size_t nn = (size_t)n;
+  double* dX = scan_upload(b, points, 3 * nn);
+  uint8_t* dK = keep ? scan_upload(b, keep, nn) : nullptr;
+  float* dF = nfeat > 0 ? scan_upload(b, features, (size_t)nfeat * nn) : nullptr;
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
+  EvTimer t;
+  CloudVox V;
+  int rc = cloud_voxels_dev(b, dX, dK, nn, dF, nfeat, nullptr, nullptr, 0, voxel_size, cap, &V, nullptr);
+  if (rc == MGS_ECAPACITY) { *out_nvox = (int32_t)V.nvox; return rc; }      // 0xffffffff = -1: the grid itself
+  if (rc != MGS_OK) return rc;
+  rc = t.finish(kernel_ms);
+  if (rc != MGS_OK) return rc;
+  const size_t nv = V.nvox;
+  if (nv > 0) {
+    HIPCHK(hipMemcpy(out_points, V.vpts, 3 * nv * sizeof(double), hipMemcpyDeviceToHost));
+    if (nfeat > 0) HIPCHK(hipMemcpy(out_features, V.vfeat, (size_t)nfeat * nv * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_count) HIPCHK(hipMemcpy(out_count, V.vcnt, nv * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  *out_nvox = (int32_t)nv;
+  return MGS_OK;
+}
+
+int mgs_scan_fps(int device, const double* points, int n, int k, double bucket_size, int32_t* out_idx,
+                 int64_t* out_nevals, double* kernel_ms) {
+  if (n < 0 || k < 0 || (k > 0 && n == 0) || k > n) return fail(MGS_EINVAL, "mgs_scan_fps: need 0 <= k <= n%s");
+  if (!cloud_size_ok(bucket_size)) return fail(MGS_EINVAL, "mgs_scan_fps: bucket_size must be positive and finite%s");
+  if (k > 0 && (!points || !out_idx)) return fail(MGS_EINVAL, "mgs_scan_fps: null argument%s");
+  if (k > 0)
+    for (size_t j = 0; j < 3 * (size_t)n; j++)
+      if (!(fabs(points[j]) <= 1.7976931348623157e308)) return fail(MGS_EINVAL, "mgs_scan_fps: a point is not finite%s");
+  if (k == 0) {
+    if (out_nevals) *out_nevals = 0;
+    return MGS_OK;
+  }
+  HIPCHK(hipSetDevice(device));
+  DevBufs b;
+  double* dX = scan_upload(b, points, 3 * (size_t)n);
+  int32_t* dO = b.get<int32_t>((size_t)k);
+  cloud_u64* dEv = b.get<cloud_u64>(1);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
+  EvTimer t;
+  int rc = cloud_fps_dev(b, dX, n, k, bucket_size, dO, dEv);
+  if (rc != MGS_OK) return rc;
+  rc = t.finish(kernel_ms);
+  if (rc != MGS_OK) return rc;
+  cloud_u64 ev = 0;
+  HIPCHK(hipMemcpy(&ev, dEv, sizeof(ev), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out_idx, dO, (size_t)k * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (out_nevals) *out_nevals = (int64_t)ev;
+  return MGS_OK;
+}
+
+int mgs_scan_cloud(int device, const mgs_scan_scene* scene, int nview, const double* cam_pos, const double* cam_rot,
+                   int width, int height, double fx, double fy, double cx, double cy, const double* extrinsics,
+                   double pfx, double pfy, double pcx, double pcy, int erode_iters, const double* region,
+                   const float* colors, int ncolor, double voxel_size, int num_points, float* out_points,
+                   float* out_colors, int32_t* out_n, int64_t* out_stats, double* stage_ms) {
+  if (!scene) return fail(MGS_EINVAL, "mgs_scan_cloud: null scene%s");
+  if (nview < 0 || width < 0 || height < 0 || num_points < 0 || ncolor < 0)
+    return fail(MGS_EINVAL, "mgs_scan_cloud: negative size%s");
+  if (nview > 65535) return fail(MGS_EINVAL, "mgs_scan_cloud: at most 65535 views per call%s");
+  if (!(fx > 0.0) || !(fy > 0.0) || !(pfx > 0.0) || !(pfy > 0.0))
+    return fail(MGS_EINVAL, "mgs_scan_cloud: focal lengths must be positive%s");
+  if (erode_iters < 0 || erode_iters > 64) return fail(MGS_EINVAL, "mgs_scan_cloud: erode_iters must be 0 .. 64%s");
+  if (!cloud_size_ok(voxel_size)) return fail(MGS_EINVAL, "mgs_scan_cloud: voxel_size must be positive and finite%s");
+  const char* bad = scan_scene_error(scene);
+  if (bad[0]) return fail(MGS_EINVAL, "mgs_scan_cloud: scene: %s", bad);
+  for (int d = 0; d < scene->ndraw; d++)
+    if (scene->draw_id[d] < 0 || scene->draw_id[d] >= ncolor)
+      return fail(MGS_EINVAL, "mgs_scan_cloud: a draw_id has no row of colors%s");
+  const size_t n = (size_t)nview * (size_t)width * (size_t)height;
+  if (n > (size_t)1 << 30) return fail(MGS_EINVAL, "mgs_scan_cloud: more than 2^30 pixels%s");
+  if (!out_n || (ncolor > 0 && !colors) || (num_points > 0 && (!out_points || !out_colors)) ||
+      (n > 0 && (!cam_pos || !cam_rot || !extrinsics)))
+    return fail(MGS_EINVAL, "mgs_scan_cloud: null argument%s");
+  if (out_stats) for (int i = 0; i < 8; i++) out_stats[i] = 0;
+  if (stage_ms) for (int i = 0; i < 4; i++) stage_ms[i] = 0.0;
+  if (n == 0) { *out_n = 0; return MGS_OK; }
+  static const double ref_region[6] = {-0.25, -0.25, -0.01, 0.25, 0.25, 1.0};
+  const double* rg = region ? region : ref_region;
+  HIPCHK(hipSetDevice(device));
+  DevBufs b;
+  ScanDev S = scan_upload_scene(b, scene);
+  double* dCP = scan_upload(b, cam_pos, 3 * (size_t)nview);
+  double* dCR = scan_upload(b, cam_rot, 9 * (size_t)nview);
+  double* dE = scan_upload(b, extrinsics, 16 * (size_t)nview);
+  float* dCol = scan_upload(b, colors, 3 * (size_t)ncolor);
+  double* dD = b.get<double>(n);
+  double* dD32 = b.get<double>(n);
+  int32_t* dS = b.get<int32_t>(n);
+  int32_t* dT = b.get<int32_t>(n);
+  int32_t* dN = b.get<int32_t>(n);
+  double* dP = b.get<double>(3 * n);
+  uint8_t* dK = b.get<uint8_t>(n);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
+  CloudEvents ev;
+  const unsigned pix_blocks = (unsigned)((n + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK);
+  hipEventRecord(ev.e[0], nullptr);
+  hipLaunchKernelGGL(mgs_scan_kernel,
+                     dim3((width + MGS_SCAN_TILE - 1) / MGS_SCAN_TILE, (height + MGS_SCAN_TILE - 1) / MGS_SCAN_TILE, nview),
+                     dim3(MGS_SCAN_TILE * MGS_SCAN_TILE), 0, nullptr, S, dCP, dCR, width, height, fx, fy, cx, cy, dD, dS,
+                     dT, dN);
+  hipEventRecord(ev.e[1], nullptr);
+  hipLaunchKernelGGL(cloud_round_f32_kernel, dim3(pix_blocks), dim3(MGS_CLOUD_BLOCK), 0, nullptr, dD, n, dD32);
+  hipLaunchKernelGGL(mgs_scan_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, nview, width,
+                     height, dD32, dS, dE, pfx, pfy, pcx, pcy, erode_iters, rg[0], rg[1], rg[2], rg[3], rg[4], rg[5], dP,
+                     dK);
+  HIPCHK(hipGetLastError());
+  CloudVox V;
+  int rc = cloud_voxels_dev(b, dP, dK, n, nullptr, 3, dS, dCol, ncolor, voxel_size, -1, &V, ev.e[2]);
+  if (rc != MGS_OK) return rc;
+  hipEventRecord(ev.e[3], nullptr);
+  const int nvox = (int)V.nvox;
+  const int m = nvox >= num_points ? num_points : nvox;
+  cloud_u64 evals = 0;
+  float *oP = nullptr, *oC = nullptr;
+  if (m > 0) {
+    oP = b.get<float>(3 * (size_t)m);
+    oC = b.get<float>(3 * (size_t)m);
+    int32_t* dIdx = nullptr;
+    cloud_u64* dEv = nullptr;
+    if (nvox >= num_points) {
+      double* dX = b.get<double>(3 * (size_t)nvox);
+      dIdx = b.get<int32_t>((size_t)m);
+      dEv = b.get<cloud_u64>(1);
+      if (!b.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
+      hipLaunchKernelGGL(cloud_round_f32_kernel, dim3((3 * (unsigned)nvox + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK),
+                         dim3(MGS_CLOUD_BLOCK), 0, nullptr, V.vpts, 3 * (size_t)nvox, dX);
+      rc = cloud_fps_dev(b, dX, nvox, m, 8.0 * voxel_size, dIdx, dEv);
+      if (rc != MGS_OK) return rc;
+    }
+    if (!b.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
+    hipLaunchKernelGGL(cloud_gather_kernel, dim3((m + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK), dim3(MGS_CLOUD_BLOCK), 0,
+                       nullptr, dIdx, m, V.vpts, V.vfeat, oP, oC);
+    if (dEv) {
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpy(&evals, dEv, sizeof(evals), hipMemcpyDeviceToHost));
+    }
+  }
+  hipEventRecord(ev.e[4], nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventSynchronize(ev.e[4]));
+  if (m > 0) {
+    HIPCHK(hipMemcpy(out_points, oP, 3 * (size_t)m * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_colors, oC, 3 * (size_t)m * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  *out_n = m;
+  if (stage_ms)
+    for (int i = 0; i < 4; i++) {
+      float f = 0.f;
+      hipEventElapsedTime(&f, ev.e[i], ev.e[i + 1]);
+      stage_ms[i] = f;
+    }
+  if (out_stats) {
+    out_stats[0] = V.npts;
+    out_stats[1] = nvox;
+    out_stats[2] = (int64_t)evals;
+    out_stats[3] = V.ncell;
+    out_stats[4] = m;
+    out_stats[5] = (int64_t)n;
+  }
+  return MGS_OK;
 }
 
 int mgs_max_rows(void) { return 64 * MGS_RPL; }

@@ -88,6 +88,13 @@ def load_library(wide: bool = False):
                                   ctypes.c_int, c_d, c_d, c_d, c_d, P(c_d), P(c_i), P(c_i), P(c_i), P(c_d)]
     L.mgs_scan_points.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(c_d), P(c_i), P(c_d),
                                   c_d, c_d, c_d, c_d, ctypes.c_int, P(c_d), P(c_d), P(c_u8), P(c_d)]
+    c_f, c_i64 = ctypes.c_float, ctypes.c_int64
+    L.mgs_scan_voxels.argtypes = [ctypes.c_int, ctypes.c_int, P(c_d), P(c_u8), ctypes.c_int, P(c_f), c_d, ctypes.c_int,
+                                  P(c_d), P(c_f), P(c_i), P(c_i), P(c_d)]
+    L.mgs_scan_fps.argtypes = [ctypes.c_int, P(c_d), ctypes.c_int, ctypes.c_int, c_d, P(c_i), P(c_i64), P(c_d)]
+    L.mgs_scan_cloud.argtypes = [ctypes.c_int, P(abi.ScanScene), ctypes.c_int, P(c_d), P(c_d), ctypes.c_int,
+                                 ctypes.c_int, c_d, c_d, c_d, c_d, P(c_d), c_d, c_d, c_d, c_d, ctypes.c_int, P(c_d),
+                                 P(c_f), ctypes.c_int, c_d, ctypes.c_int, P(c_f), P(c_f), P(c_i), P(c_i64), P(c_d)]
     L.mgs_supports_nv.argtypes = [ctypes.c_int]
     L.mgs_supports_nv.restype = ctypes.c_int
     L.mgs_rollout_grid.argtypes = [vp, ctypes.c_int]
@@ -607,6 +614,118 @@ def scan_points(depth, seg, extrinsics, fx, fy, cx, cy, erode_iters=5, region=No
                              None if rg is None else ptr(rg, ctypes.c_double), ptr(pts, ctypes.c_double),
                              ptr(keep, ctypes.c_uint8), ctypes.byref(ms)), "mgs_scan_points", L)
     return pts, keep.astype(bool), ms.value
+
+
+def scan_voxels(points, features=None, voxel_size=0.002, keep=None, device=0):
+    """mgs.util.img_proc.voxel_downsample_pcd(points[keep], features[keep],
+    voxel_size) on the GPU, bit for bit (mgs_scan_voxels): points (n, 3) f64,
+    features (n, nfeat) float32 or None, keep (n,) bool or None.  Returns
+    (points (nvox, 3) f64, features (nvox, nfeat) float32, count (nvox,) int32,
+    kernel ms)."""
+    x = np.asarray(points)
+    if x.ndim != 2 or x.shape[1] != 3:
+        raise ValueError("points are (n, 3)")
+    x = np.ascontiguousarray(x, np.float64)
+    n = len(x)
+    if features is None:
+        f = np.zeros((n, 0), np.float32)
+    else:
+        f = np.asarray(features)
+        if f.ndim != 2 or len(f) != n:
+            raise ValueError("features are (n, nfeat), one row per point")
+        if f.dtype != np.float32:
+            raise ValueError("features are float32 (the sums are taken in the features' precision)")
+        f = np.ascontiguousarray(f)
+    k = None
+    if keep is not None:
+        k = np.asarray(keep)
+        if k.shape != (n,) or k.dtype not in (np.bool_, np.uint8):
+            raise ValueError("keep is (n,) bool")
+        k = np.ascontiguousarray(k != 0, np.uint8)
+    if not (np.isfinite(voxel_size) and voxel_size > 0):
+        raise ValueError("voxel_size must be positive and finite")
+    L = _device_lib(device)
+    nfeat = f.shape[1]
+    cap = n if k is None else int(k.sum())
+    oP, oF, oC = np.zeros((cap, 3)), np.zeros((cap, nfeat), np.float32), np.zeros(cap, np.int32)
+    nvox, ms = ctypes.c_int32(0), ctypes.c_double(0.0)
+    _check(L.mgs_scan_voxels(device, n, ptr(x, ctypes.c_double), None if k is None else ptr(k, ctypes.c_uint8), nfeat,
+                             ptr(f, ctypes.c_float) if nfeat and n else None, float(voxel_size), cap,
+                             ptr(oP, ctypes.c_double), ptr(oF, ctypes.c_float), ptr(oC, ctypes.c_int32),
+                             ctypes.byref(nvox), ctypes.byref(ms)), "mgs_scan_voxels", L)
+    m = nvox.value
+    return oP[:m], oF[:m], oC[:m], ms.value
+
+
+def scan_fps(points, k, bucket_size, device=0):
+    """the indices of contact_fps by the spatially pruned pick (mgs_scan_fps):
+    (indices (k,), point-distance evaluations, kernel ms); a sweep evaluates
+    n (k - 1) distances"""
+    x = np.asarray(points)
+    if x.ndim != 2 or x.shape[1] != 3:
+        raise ValueError("points are (n, 3)")
+    k = int(k)
+    if k < 0 or k > len(x):
+        raise ValueError("need 0 <= k <= n")
+    if not (np.isfinite(bucket_size) and bucket_size > 0):
+        raise ValueError("bucket_size must be positive and finite")
+    x = np.ascontiguousarray(x, np.float64)
+    L = _device_lib(device)
+    out = np.zeros(k, np.int32)
+    nev, ms = ctypes.c_int64(0), ctypes.c_double(0.0)
+    _check(L.mgs_scan_fps(device, ptr(x, ctypes.c_double), len(x), k, float(bucket_size), ptr(out, ctypes.c_int32),
+                          ctypes.byref(nev), ctypes.byref(ms)), "mgs_scan_fps", L)
+    return out, nev.value, ms.value
+
+
+CLOUD_STATS = ("kept", "voxels", "pick_evals", "grid_cells", "rows", "pixels")
+CLOUD_STAGES = ("render_ms", "points_compact_ms", "voxels_ms", "pick_ms")
+
+
+def scan_cloud(scene_arrays, cam_pos, cam_rot, width, height, fx, fy, cx, cy, extrinsics, pfx, pfy, pcx, pcy, colors,
+               num_points, voxel_size=0.002, erode_iters=5, region=None, device=0):
+    """scene -> sampled cloud with every intermediate on the GPU
+    (mgs_scan_cloud): render as scan_render (fx .. cy), points as scan_points on
+    the float32-rounded depth (extrinsics, pfx .. pcy, erode_iters, region), the
+    voxel grid of scan_voxels with the float32 rows colors[draw_id] as features,
+    the pick of scan_fps among the float32-rounded voxels when there are at
+    least num_points.  Returns (points (m, 3) float32, colors (m, 3) float32,
+    dict of CLOUD_STATS and CLOUD_STAGES)."""
+    from mgs.scan.scene import pack_scene
+    cp = np.ascontiguousarray(cam_pos, np.float64).reshape(-1, 3)
+    cr = np.ascontiguousarray(cam_rot, np.float64).reshape(-1, 3, 3)
+    e = np.asarray(extrinsics, np.float64)
+    if len(cp) != len(cr) or e.shape != (len(cp), 4, 4):
+        raise ValueError("one rotation and one 4 x 4 extrinsic per camera position")
+    e = np.ascontiguousarray(e)
+    col = np.asarray(colors)
+    if col.ndim != 2 or col.shape[1] != 3:
+        raise ValueError("colors are (ncolor, 3)")
+    col = np.ascontiguousarray(col, np.float32)
+    num_points = int(num_points)
+    if min(int(width), int(height), num_points) < 0:
+        raise ValueError("negative size")
+    if not (np.isfinite(voxel_size) and voxel_size > 0):
+        raise ValueError("voxel_size must be positive and finite")
+    rg = None if region is None else np.ascontiguousarray(region, np.float64).reshape(-1)
+    if rg is not None and rg.shape != (6,):
+        raise ValueError("region is (lo xyz, hi xyz)")
+    L = _device_lib(device)
+    scene, keep = pack_scene(scene_arrays)
+    oP, oC = np.zeros((num_points, 3), np.float32), np.zeros((num_points, 3), np.float32)
+    n = ctypes.c_int32(0)
+    stats, stages = np.zeros(8, np.int64), np.zeros(4)
+    d = ctypes.c_double
+    _check(L.mgs_scan_cloud(device, ctypes.byref(scene), len(cp), ptr(cp, d), ptr(cr, d), int(width), int(height),
+                            float(fx), float(fy), float(cx), float(cy), ptr(e, d), float(pfx), float(pfy), float(pcx),
+                            float(pcy), int(erode_iters), None if rg is None else ptr(rg, d),
+                            ptr(col, ctypes.c_float), len(col), float(voxel_size), num_points,
+                            ptr(oP, ctypes.c_float), ptr(oC, ctypes.c_float), ctypes.byref(n),
+                            ptr(stats, ctypes.c_int64), ptr(stages, d)), "mgs_scan_cloud", L)
+    del keep
+    info = {k: int(v) for k, v in zip(CLOUD_STATS, stats)}
+    info.update({k: float(v) for k, v in zip(CLOUD_STAGES, stages)})
+    return oP[:n.value], oC[:n.value], info
 
 
 def contact_seeds(seeds, radius, rng_seed, ntip, device=0):

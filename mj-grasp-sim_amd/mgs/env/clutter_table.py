@@ -143,6 +143,7 @@ class ClutterTableEnv:
         self._scan_meshes = {}
         self.table_rgba = None
         self.last_scan = None
+        self.last_cloud = None
 
     def _check_kernel(self, nv):
         """the kernels hold up to 128 dofs (lanes over dofs: one per lane up to
@@ -702,6 +703,30 @@ class ClutterTableEnv:
         rgbd = np.concatenate([colors[seg], res["depth"].astype(np.float32)[..., None]], axis=-1)
         self.last_scan = res
         return rgbd, extr, erode_mask(seg != -1, 5), seg
+
+    def scan_cloud(self, num_images, num_points=15000, voxel_size=0.002, width=480, height=480):
+        """the cloud render_scene_processed writes, with everything between the
+        scene and the sampled points on the GPU (mgs_scan_cloud): the views of
+        `scan`, points by get_camera_intrinsics from the float32 depth, eroded
+        mask, region crop, voxel grid, farthest-point pick.  Returns (points
+        (m, 3), colors (m, 3)) float32, m = num_points or, with fewer voxels
+        than that, every voxel.  `last_cloud` keeps the counts and stage times
+        (mgs.core.engine.CLOUD_STATS, CLOUD_STAGES)."""
+        from mgs.core.engine import scan_cloud
+        from mgs.scan.scene import REGION
+        self.scan_width, self.scan_height = int(width), int(height)
+        extr = []
+        for i in range(num_images):
+            self.update_camera_settings(num_images, i)
+            extr.append(self.get_camera_extrinsics())
+        extr = np.stack(extr, axis=0) if extr else np.zeros((0, 4, 4))
+        K, Kp = self.get_render_intrinsics(), self.get_camera_intrinsics()
+        points, colors, info = scan_cloud(self.scan_scene().arrays(), extr[:, :3, 3], extr[:, :3, :3], width, height,
+                                          K[0, 0], K[1, 1], K[0, 2], K[1, 2], extr, Kp[0, 0], Kp[1, 1], Kp[0, 2],
+                                          Kp[1, 2], self.scan_colors(), num_points, voxel_size=voxel_size,
+                                          erode_iters=5, region=REGION, device=self.device)
+        self.last_cloud = info
+        return points, colors
 
     def scan_colors(self) -> np.ndarray:
         """flat colour per entry of scan_geom_names: the table's from the scene
