@@ -663,8 +663,11 @@ int mgs_contact_optimize(int device, const mgs_kin_desc* kin, int n, const doubl
  * above changes; the ABI version stays).  Host pointers, synchronous on
  * `device`; kernel_ms (may be NULL) = kernel duration.
  *
- * A scene is a list of drawables -- boxes and spheres given by pose and size,
- * mesh instances given by pose and a mesh index -- and, per distinct mesh, a
+ * A scene is a list of drawables -- boxes, spheres, capsules and capped
+ * cylinders given by pose and size (a capsule's or cylinder's axis is its
+ * frame's z, MuJoCo's convention; its radius must be finite and > 0, its
+ * half-length finite and >= 0, MGS_EINVAL otherwise), mesh instances given by
+ * pose and a mesh index -- and, per distinct mesh, a
  * threaded bounding-volume hierarchy: the nodes of mesh m are
  * mesh_node0[m] .. mesh_node0[m + 1] - 1 in depth-first order, so node i + 1 is
  * the first child of an inner node i (node_count == 0) and node_skip[i] (an
@@ -679,6 +682,8 @@ int mgs_contact_optimize(int device, const mgs_kin_desc* kin, int n, const doubl
 #define MGS_SCAN_BOX 0
 #define MGS_SCAN_SPHERE 1
 #define MGS_SCAN_MESH 2
+#define MGS_SCAN_CAPSULE 3
+#define MGS_SCAN_CYLINDER 4
 typedef struct mgs_scan_scene {
   int32_t ndraw, nmesh, nnode, ntri;
   int32_t *draw_type;        /* ndraw: MGS_SCAN_* */
@@ -686,7 +691,8 @@ typedef struct mgs_scan_scene {
   int32_t *draw_mesh;        /* ndraw: mesh index of a mesh instance (else ignored) */
   double *draw_pos;          /* ndraw * 3: geom frame origin, world */
   double *draw_rot;          /* ndraw * 9: geom frame axes (row-major, frame -> world) */
-  double *draw_size;         /* ndraw * 3: box half extents; sphere radius first */
+  double *draw_size;         /* ndraw * 3: box half extents; sphere radius first;
+                                capsule / cylinder radius first, half-length second */
   int32_t *mesh_node0;       /* nmesh + 1 */
   int32_t *mesh_tri0;        /* nmesh + 1 */
   double *node_box;          /* nnode * 6: min xyz, max xyz (mesh frame) */
@@ -704,9 +710,12 @@ typedef struct mgs_scan_scene {
  * is the planar depth.  The nearest hit is the lexicographic minimum of
  * (t, drawable index, face id) over hits with t > 0: triangles two-sided
  * (Moeller-Trumbore as mgs_antipodal_contacts), a sphere's smallest positive
- * root, a box's entry or, from inside, its exit.  Outputs, nview * height *
+ * root, a box's entry or, from inside, its exit, a capsule's or cylinder's
+ * smallest positive root over its pieces (side for |z| <= half-length; a
+ * cylinder's caps within the radius; a capsule's end spheres, each on its
+ * outer half), which from inside is the exit too.  Outputs, nview * height *
  * width each: out_depth (t, 0 on a miss), out_seg (draw_id, -1 on a miss),
- * out_tri (face id, -1 for a box, a sphere or a miss), out_ntest (ray-triangle
+ * out_tri (face id, -1 for a primitive or a miss), out_ntest (ray-triangle
  * tests the pixel performed; may be NULL).  The scene's index arrays are
  * checked (MGS_EINVAL) before anything is launched. */
 int mgs_scan_render(int device, const mgs_scan_scene* scene, int nview, const double* cam_pos,

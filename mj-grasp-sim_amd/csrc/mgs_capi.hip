@@ -1086,8 +1086,20 @@ const char* scan_scene_error(const mgs_scan_scene* s) {
   }
   for (int d = 0; d < s->ndraw; d++) {
     const int t = s->draw_type[d];
-    if (t != MGS_SCAN_BOX && t != MGS_SCAN_SPHERE && t != MGS_SCAN_MESH) return "unknown drawable type";
+    if (t != MGS_SCAN_BOX && t != MGS_SCAN_SPHERE && t != MGS_SCAN_MESH && t != MGS_SCAN_CAPSULE &&
+        t != MGS_SCAN_CYLINDER)
+      return "unknown drawable type";
     if (t == MGS_SCAN_MESH && (s->draw_mesh[d] < 0 || s->draw_mesh[d] >= s->nmesh)) return "mesh index out of range";
+    if (t == MGS_SCAN_CAPSULE || t == MGS_SCAN_CYLINDER) {
+      const double r = s->draw_size[3 * (size_t)d], h = s->draw_size[3 * (size_t)d + 1];
+      // written so that a NaN fails: radius finite and > 0, half-length finite and >= 0
+      if (!(r > 0.0 && r <= 1.7976931348623157e308 && h >= 0.0 && h <= 1.7976931348623157e308)) {
+        static thread_local char msg[96];
+        snprintf(msg, sizeof(msg), "drawable %d: a %s needs a finite radius > 0 and a finite half-length >= 0", d,
+                 t == MGS_SCAN_CAPSULE ? "capsule" : "cylinder");
+        return msg;
+      }
+    }
   }
   return "";
 }

@@ -14,7 +14,9 @@
 // does not depend on that order; ntest counts the ray-triangle tests, which
 // does.  Triangles go through ray_tri (mgs_sampler.hip); all arithmetic is f64
 // without contraction, expression for expression what tests/scan_truth.py
-// restates in numpy.
+// restates in numpy.  Capsules and capped cylinders (a gripper's collision
+// geometry, GripperScanEnv) go through scan_rod in the geom frame the box
+// branch uses; tests/gripper_scan_truth.py restates it.
 //
 // mgs_scan_points_kernel: one lane per pixel: the valid mask (seg != -1) eroded
 // erode_iters times by a 3 x 3 square with the outside counted as set -- the
@@ -55,6 +57,57 @@ DEVI int scan_slab(const double* o, const double* d, const double* inv, const do
   *tn = tnear;
   *tf = tfar;
   return tnear <= tfar;
+}
+
+// the ray om + t dm (geom frame) against a rod of radius r and half-length h
+// about the frame's z: a capped cylinder (cyl != 0) or a capsule.  Returns the
+// smallest t > 0 over the pieces -- from inside that is the exit -- or INFINITY.
+//   side  (dm0^2 + dm1^2) t^2 + 2 (om0 dm0 + om1 dm1) t + (om0^2 + om1^2 - r^2) = 0,
+//         a root counts where |om2 + t dm2| <= h; no side test if dm0^2 + dm1^2 == 0
+//   caps  t = (+-h - om2) / dm2, counts where x^2 + y^2 <= r^2; none if dm2 == 0
+//   ends  the spheres about (0, 0, +-h), each root only on its outer half,
+//         +-(z -+ h) >= 0
+// cyl is the same for every lane of a wave (one drawable at a time).
+DEVI double scan_rod(const double* om, const double* dm, double r, double h, int cyl) {
+  double t = INFINITY;
+  const double rr = r * r;
+  const double a = dm[0] * dm[0] + dm[1] * dm[1];
+  if (a > 0.0) {
+    double b = om[0] * dm[0] + om[1] * dm[1];
+    double c = (om[0] * om[0] + om[1] * om[1]) - rr;
+    double disc = b * b - a * c;
+    if (disc >= 0.0) {
+      double s = sqrt(disc);
+      double t0 = (-b - s) / a, t1 = (-b + s) / a;
+      if (t0 > 0.0 && fabs(om[2] + t0 * dm[2]) <= h && t0 < t) t = t0;
+      if (t1 > 0.0 && fabs(om[2] + t1 * dm[2]) <= h && t1 < t) t = t1;
+    }
+  }
+  if (cyl) {
+    if (dm[2] != 0.0) {
+      for (int e = 0; e < 2; e++) {
+        double tc = ((e ? -h : h) - om[2]) / dm[2];
+        double x = om[0] + tc * dm[0], y = om[1] + tc * dm[1];
+        if (tc > 0.0 && (x * x + y * y) <= rr && tc < t) t = tc;
+      }
+    }
+    return t;
+  }
+  const double A = a + dm[2] * dm[2];
+  for (int e = 0; e < 2; e++) {
+    const double sg = e ? -1.0 : 1.0;
+    double w = om[2] - sg * h;
+    double B = (om[0] * dm[0] + om[1] * dm[1]) + w * dm[2];
+    double C = ((om[0] * om[0] + om[1] * om[1]) + w * w) - rr;
+    double disc = B * B - A * C;
+    if (disc >= 0.0) {
+      double s = sqrt(disc);
+      double t0 = (-B - s) / A, t1 = (-B + s) / A;
+      if (t0 > 0.0 && sg * (w + t0 * dm[2]) >= 0.0 && t0 < t) t = t0;
+      if (t1 > 0.0 && sg * (w + t1 * dm[2]) >= 0.0 && t1 < t) t = t1;
+    }
+  }
+  return t;
 }
 
 __global__ void __launch_bounds__(MGS_SCAN_TILE * MGS_SCAN_TILE)
@@ -127,6 +180,11 @@ mgs_scan_kernel(ScanDev S, const double* __restrict__ cam_pos, const double* __r
           double t = tn > 0.0 ? tn : tf;     // from inside: the exit
           if (t > 0.0 && t < best_t) { best_t = t; best_draw = di; best_seg = s_int[3 * j + 1]; best_face = -1; }
         }
+        continue;
+      }
+      if (type == MGS_SCAN_CAPSULE || type == MGS_SCAN_CYLINDER) {
+        double t = scan_rod(om, dm, size[0], size[1], type == MGS_SCAN_CYLINDER);
+        if (t < best_t) { best_t = t; best_draw = di; best_seg = s_int[3 * j + 1]; best_face = -1; }
         continue;
       }
       const int mesh = s_int[3 * j + 2];

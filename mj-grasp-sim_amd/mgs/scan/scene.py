@@ -1,7 +1,8 @@
 """Scan scene: the drawables a ray caster sees and the arrays mgs_scan_render
 takes (include/mgs_gpu.h, mgs_scan_scene).
 
-Drawables are boxes and spheres (pose, size) and mesh instances (pose, mesh).
+Drawables are boxes, spheres, capsules and capped cylinders (pose, size) and
+mesh instances (pose, mesh).
 Meshes are instanced: two drawables with the same `key` share one BVH
 (mgs/scan/bvh.py).  A drawable's index in the list is its rank in the
 nearest-hit order (t, drawable index, face id); its `seg_id` is what the
@@ -17,6 +18,7 @@ from mgs.core import abi
 from mgs.scan.bvh import MeshBVH, build_bvh
 
 BOX, SPHERE, MESH = abi.MGS["MGS_SCAN_BOX"], abi.MGS["MGS_SCAN_SPHERE"], abi.MGS["MGS_SCAN_MESH"]
+CAPSULE, CYLINDER = abi.MGS["MGS_SCAN_CAPSULE"], abi.MGS["MGS_SCAN_CYLINDER"]
 
 # the reference's crop of the pile (render_scene_processed.py:49-53), lo xyz, hi xyz
 REGION = np.array([-0.25, -0.25, -0.01, 0.25, 0.25, 1.0])
@@ -50,6 +52,15 @@ class ScanScene:
 
     def add_sphere(self, seg_id, pos, radius):
         return self._add(SPHERE, seg_id, pos, None, [radius, 0.0, 0.0])
+
+    def add_capsule(self, seg_id, pos, rot, radius, half_length):
+        """a capsule about the frame's z: the segment (0, 0, +-half_length) swept
+        by a ball of `radius`"""
+        return self._add(CAPSULE, seg_id, pos, rot, [radius, half_length, 0.0])
+
+    def add_cylinder(self, seg_id, pos, rot, radius, half_length):
+        """a capped cylinder about the frame's z"""
+        return self._add(CYLINDER, seg_id, pos, rot, [radius, half_length, 0.0])
 
     def add_mesh(self, seg_id, pos, rot, verts=None, faces=None, key=None):
         """a mesh instance; `key` names the mesh (instances of one key share its

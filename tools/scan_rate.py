@@ -5,8 +5,11 @@ icosahedron subdivided 4 times, the size class of a deep tree).  Prints one
 JSON line per case: rays/s and kernel_ms of mgs_scan_render, the mean
 ray-triangle tests per ray, kernel_ms of mgs_scan_points, and the host costs
 around them (scene + BVH build, rgbd_to_pcd, voxel_downsample_pcd at 2 mm).
+A last line is the gripper scan: the Shadow hand's collision geometry
+(capsules, cylinders, boxes, spheres, hulls) from 10 views of 480 x 480
+(GripperScanEnv.scan).
 
-    python tools/scan_rate.py [--views 32] [--size 480] [--repeat 3]
+    python tools/scan_rate.py [--views 32] [--size 480] [--repeat 3] [--gripper-views 10]
 """
 import argparse
 import json
@@ -66,11 +69,41 @@ def measure(env, label, views, size, repeat):
         "host_voxel_downsample_s": round(t_vox, 3), "voxels": int(len(vox))}), flush=True)
 
 
+def measure_gripper(views, size, repeat):
+    """GripperScanEnv.scan of the open Shadow hand: kernel time by HIP events,
+    median of `repeat` after a first call"""
+    from mgs.env.gripper_scan import GripperScanEnv
+    from mgs.gripper.shadow import GripperShadowRight
+    from mgs.util.geo.transforms import SE3Pose
+    env = GripperScanEnv(GripperShadowRight(SE3Pose(np.zeros(3), np.array([1.0, 0, 0, 0]), "wxyz")))
+    t0 = time.perf_counter()
+    scene = env.scan_scene()
+    S = scene.arrays()
+    t_scene = time.perf_counter() - t0
+    ms = []
+    for _ in range(repeat + 1):
+        _, _, masks, seg = env.scan(num_images=views, width=size, height=size)
+        ms.append(env.last_scan["kernel_ms"])
+    ms = ms[1:]
+    rays = views * size * size
+    kinds = np.bincount(S["draw_type"], minlength=5)
+    print(json.dumps({
+        "case": "gripper_shadow", "views": views, "width": size, "height": size, "drawables": int(scene.ndraw),
+        "boxes": int(kinds[0]), "spheres": int(kinds[1]), "hulls": int(kinds[2]), "capsules": int(kinds[3]),
+        "cylinders": int(kinds[4]), "triangles": int(sum(m.ntri for m in scene.meshes)),
+        "kernel_ms": round(float(np.median(ms)), 3), "kernel_ms_runs": [round(float(x), 3) for x in ms],
+        "rays_per_s": round(rays / (np.median(ms) * 1e-3)),
+        "mean_ntest_per_ray": round(float(env.last_scan["ntest"].mean()), 3),
+        "hit_fraction": round(float((seg != -1).mean()), 4), "masked_fraction": round(float(masks.mean()), 4),
+        "host_scene_build_s": round(t_scene, 3)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--views", type=int, default=32)
     ap.add_argument("--size", type=int, default=480)
     ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--gripper-views", type=int, default=10)
     a = ap.parse_args()
     import torch
     if torch.cuda.is_available():
@@ -82,6 +115,8 @@ def main():
     ball = icosphere(4, radius=0.04)
     env._scan_meshes = {os.path.join(o.asset_dir, o.info()["original_file"]): ball for o in env.objects}
     measure(env, "sphere_5120_faces", a.views, a.size, a.repeat)
+    if a.gripper_views > 0:      # 0: the pile rows alone (a library from before the gripper scan)
+        measure_gripper(a.gripper_views, a.size, a.repeat)
 
 
 if __name__ == "__main__":
