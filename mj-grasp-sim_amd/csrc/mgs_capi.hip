@@ -4,6 +4,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -34,6 +35,48 @@ int fail(int code, const char* fmt, const char* what = "") {
     hipError_t _e = (expr);                                                           \
     if (_e != hipSuccess) return fail(MGS_EHIP, "HIP error: %s", hipGetErrorString(_e)); \
   } while (0)
+
+// written so that a NaN fails
+bool is_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
+
+// The host layer's rule: the device memory of one call lives in a DevBufs,
+// freed on every return path; mgs_model and mgs_batch own theirs
+// (mgs_model_free, mgs_batch_close); launches name their arguments.
+struct DevBufs {
+  std::vector<void*> p;
+  bool ok = true;
+  template <class T>
+  T* get(size_t n) {
+    void* q = nullptr;
+    if (hipMalloc(&q, (n > 0 ? n : 1) * sizeof(T)) != hipSuccess) { ok = false; return nullptr; }
+    p.push_back(q);
+    return (T*)q;
+  }
+  ~DevBufs() { for (void* q : p) hipFree(q); }
+};
+// a host array on the device (b.ok turns false when the allocation or the copy fails)
+template <class T>
+T* upload(DevBufs& b, const T* src, size_t n) {
+  T* d = b.get<T>(n);
+  if (d && n > 0 && hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) b.ok = false;
+  return d;
+}
+// the time between its construction and finish() on the null stream
+struct EvTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  EvTimer() { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, nullptr); }
+  int finish(double* ms) {
+    hipEventRecord(e1, nullptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    if (e != hipSuccess) return fail(MGS_EHIP, "HIP error: %s", hipGetErrorString(e));
+    float f = 0.f;
+    hipEventElapsedTime(&f, e0, e1);
+    if (ms) *ms = f;
+    return MGS_OK;
+  }
+  ~EvTimer() { hipEventDestroy(e0); hipEventDestroy(e1); }
+};
 
 // whether a model's G rows live in HBM
 #ifdef MGS_G_GLOBAL
@@ -145,6 +188,16 @@ Lay make_layout(const mgs_model_desc& m, size_t* bytes) {
   l.total_doubles = off;
   *bytes = (size_t)off * sizeof(double);
   return l;
+}
+
+// a layout as the words mgs_model_layout exports and a specialised code object
+// bakes: o[], u[], ncon_max, nefc_max, nv, total_doubles
+constexpr int LAYOUT_WORDS = L_COUNT + U_COUNT + 4;
+void layout_words(const Lay& l, int32_t* w) {
+  int k = 0;
+  for (int i = 0; i < L_COUNT; i++) w[k++] = l.o[i];
+  for (int i = 0; i < U_COUNT; i++) w[k++] = l.u[i];
+  w[k++] = l.ncon_max; w[k++] = l.nefc_max; w[k++] = l.nv; w[k++] = l.total_doubles;
 }
 }  // namespace
 
@@ -273,37 +326,34 @@ int mgs_model_create(const mgs_model_desc* desc, const int32_t* ibuf, const doub
   }
   if (desc->nu == 0 && desc->nact != 0) return fail(MGS_EINVAL, "nact without actuators%s");
   HIPCHK(hipSetDevice(device));
-  mgs_model* m = new mgs_model();
+  // (every member null: an early return frees what has been allocated by then)
+  std::unique_ptr<mgs_model, void (*)(mgs_model*)> m(new mgs_model(), mgs_model_free);
   m->desc = *desc;
   m->device = device;
   size_t ib = sizeof(int32_t) * (desc->isize > 0 ? desc->isize : 1);
   size_t db = sizeof(double) * (desc->dsize > 0 ? desc->dsize : 1);
-  if (hipMalloc(&m->dI, ib) != hipSuccess || hipMalloc(&m->dD, db) != hipSuccess) {
-    delete m;
+  if (hipMalloc(&m->dI, ib) != hipSuccess || hipMalloc(&m->dD, db) != hipSuccess)
     return fail(MGS_ENOMEM, "device allocation failed%s");
-  }
   HIPCHK(hipMemcpy(m->dI, ibuf, sizeof(int32_t) * desc->isize, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(m->dD, dbuf, sizeof(double) * desc->dsize, hipMemcpyHostToDevice));
   m->lay = make_layout(*desc, &m->lds_bytes);
   if (m->lds_bytes > 160 * 1024 - MGS_STATIC_LDS) {
-    size_t need = m->lds_bytes;
-    mgs_model_free(m);
     char buf[64];
-    snprintf(buf, sizeof(buf), "%zu", need);
+    snprintf(buf, sizeof(buf), "%zu", m->lds_bytes);
     return fail(MGS_ECAPACITY, "per-candidate working set %s B exceeds 160 KiB LDS; lower ncon_max", buf);
   }
   // the attribute is per kernel function, shared by every model of this nv: set it
   // to the CU's whole LDS so a later, smaller model cannot lower it under an
   // earlier, wider one (occupancy follows each launch's own dynamic size)
   HIPCHK(set_lds_limit(desc->nv, 160 * 1024 - MGS_STATIC_LDS));
-  *out = m;
+  *out = m.release();
   return MGS_OK;
 }
 
 void mgs_model_free(mgs_model* m) {
   if (!m) return;
   if (m->special_mod) hipModuleUnload(m->special_mod);
-  hipFree(m->dI);
+  hipFree(m->dI);     // (null when mgs_model_create failed before it: hipFree(nullptr) is a no-op)
   hipFree(m->dD);
   delete m;
 }
@@ -311,8 +361,7 @@ void mgs_model_free(mgs_model* m) {
 int mgs_batch_open(mgs_model* model, int capacity, mgs_batch** out) {
   if (!model || capacity <= 0 || !out) return fail(MGS_EINVAL, "mgs_batch_open: bad argument%s");
   HIPCHK(hipSetDevice(model->device));
-  mgs_batch* b = new mgs_batch();
-  memset(b, 0, sizeof(*b));
+  std::unique_ptr<mgs_batch, void (*)(mgs_batch*)> b(new mgs_batch(), mgs_batch_close);
   b->m = model;
   b->cap = capacity;
   const mgs_model_desc& d = model->desc;
@@ -331,15 +380,12 @@ int mgs_batch_open(mgs_model* model, int capacity, mgs_batch** out) {
             // the counters must be zero before any stream's launch reads them
             // (hipMemset may still be in flight on the null stream otherwise)
             hipDeviceSynchronize() == hipSuccess;
-  if (!ok) {
-    mgs_batch_close(b);
-    return fail(MGS_ENOMEM, "device allocation failed%s");
-  }
+  if (!ok) return fail(MGS_ENOMEM, "device allocation failed%s");
   HIPCHK(hipEventCreate(&b->e0));
   HIPCHK(hipEventCreate(&b->e1));
   HIPCHK(hipEventCreate(&b->e2));
   HIPCHK(hipEventCreate(&b->e3));
-  *out = b;
+  *out = b.release();
   return MGS_OK;
 }
 
@@ -413,6 +459,16 @@ static int resident_workgroups(mgs_model* m) {
   }
   m->resident = per_cu * cus;
   return m->resident;
+}
+
+// the grid rule: a launch over n candidates runs as a work queue on the
+// resident workgroups (at most k of them in mode k >= 2) when those are fewer
+// than n; 0 = one workgroup per candidate, no queue
+static int queue_grid(mgs_model* m, int n) {
+  if (queue_mode() == 0) return 0;
+  int r = resident_workgroups(m);
+  if (queue_mode() > 1 && r > queue_mode()) r = queue_mode();
+  return (r > 0 && r < n) ? r : 0;
 }
 
 int mgs_model_resident(mgs_model* model) {
@@ -506,31 +562,36 @@ static int alloc_rings(mgs_batch* b, int n) {
   return MGS_OK;
 }
 
+// every queue header of a batch, once the device is idle
+static int read_queue_headers(mgs_batch* b, uint32_t (&h)[MGS_QHDR * MGS_QUEUE_RING]) {
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(h, b->d_queue, sizeof(h), hipMemcpyDeviceToHost));
+  return MGS_OK;
+}
+
 // the expired-spin counters (word 7 of every queue header), summed
 static int expired_spins(mgs_batch* b, uint64_t* out) {
   uint32_t h[MGS_QHDR * MGS_QUEUE_RING];
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(h, b->d_queue, sizeof(h), hipMemcpyDeviceToHost));
+  int rc = read_queue_headers(b, h);
+  if (rc) return rc;
   uint64_t e = 0;
   for (int k = 0; k < MGS_QUEUE_RING; k++) e += h[MGS_QHDR * k + 7];
   *out = e;
   return MGS_OK;
 }
 
-// after a rotating launch of a synchronous entry: an expired ring spin (a
-// candidate possibly lost, a ring slot possibly written after its launch
-// ended) fails the call with MGS_EQUEUE and resets every ring and ring
-// head / tail, so the next launch starts from a clean protocol state
-// before a synchronous rotating launch: expired spins left by earlier launches
-// (the device entries', which their callers audit) are acknowledged here and
-// the rings they may have left dirty are reset, so the check after this launch
-// counts only its own
-static int sync_rotation(mgs_batch* b) {
+// ring spins expired since the last look (a candidate possibly lost, a ring
+// slot possibly written after its launch ended) are acknowledged and every
+// ring and ring head / tail is reset, so the next launch starts from a clean
+// protocol state; *expired (optional) tells whether there were any
+static int reset_expired(mgs_batch* b, bool* expired = nullptr) {
+  if (expired) *expired = false;
   if (!b->d_rings) return MGS_OK;
   uint64_t e = 0;
   int rc = expired_spins(b, &e);
   if (rc) return rc;
   if (e == b->spins_seen) return MGS_OK;
+  if (expired) *expired = true;
   b->spins_seen = e;
   HIPCHK(hipMemset(b->d_rings, 0, sizeof(uint32_t) * MGS_QRING_F(b->ring_n) * MGS_QUEUE_RING));
   for (int k = 0; k < MGS_QUEUE_RING; k++)
@@ -539,58 +600,43 @@ static int sync_rotation(mgs_batch* b) {
   return MGS_OK;
 }
 
+// after a rotating launch of a synchronous entry: an expired ring spin fails
+// the call with MGS_EQUEUE
 static int check_rotation(mgs_batch* b) {
-  if (!b->d_rings) return MGS_OK;
-  uint64_t e = 0;
-  int rc = expired_spins(b, &e);
-  if (rc) return rc;
-  if (e == b->spins_seen) return MGS_OK;
-  b->spins_seen = e;
-  HIPCHK(hipMemset(b->d_rings, 0, sizeof(uint32_t) * MGS_QRING_F(b->ring_n) * MGS_QUEUE_RING));
-  for (int k = 0; k < MGS_QUEUE_RING; k++)
-    HIPCHK(hipMemset(b->d_queue + MGS_QHDR * k + 2, 0, 2 * sizeof(uint32_t)));
-  HIPCHK(hipDeviceSynchronize());
+  bool expired;
+  int rc = reset_expired(b, &expired);
+  if (rc || !expired) return rc;
   return fail(MGS_EQUEUE, "rotation ring protocol timed out (expired spin): a candidate may have been lost; "
                           "the launch's outputs are invalid%s");
 }
 
-static int launch_rollout(mgs_batch* b, const mgs_schedule* sched, int n, const double* d_qpos_init,
-                          const double* d_mocap_quat, const double* d_phase_start, const double* d_phase_target,
-                          const uint8_t* d_active, uint8_t* d_label, int32_t* d_fail_step, double* d_obj_qpos,
-                          int32_t* d_stats, const double* d_vstate, double* d_state_out, void* stream,
-                          const int32_t* d_list = nullptr, int32_t* d_count = nullptr, int grid = 0,
-                          double* d_resume_out = nullptr, const double* d_resume_in = nullptr,
-                          const double* d_mask_mpos = nullptr, int mask_pred = 0, uint8_t* d_mask_out = nullptr,
-                          int32_t* d_ovf = nullptr) {
-  if (!b || !sched || n < 0) return fail(MGS_EINVAL, "mgs_rollout_device: bad argument%s");
+// one rollout launch.  The caller names what it uses of `a` (n, the candidates'
+// inputs and outputs, the list, resume records, fused mask, overflow header);
+// md, lay, sc, queue and ovf_list are filled here.  A launch over a list runs
+// list_grid workgroups, any other the grid rule's.
+static int launch_rollout(mgs_batch* b, const mgs_schedule* sched, RolloutArgs a, void* stream, int list_grid = 0) {
+  if (!b || !sched || a.n < 0) return fail(MGS_EINVAL, "mgs_rollout_device: bad argument%s");
   if (sched->nphase < 1 || sched->nphase > MGS_MAX_PHASES) return fail(MGS_EINVAL, "bad phase count%s");
-  if (n == 0) return MGS_OK;
+  if (a.n == 0) return MGS_OK;
   HIPCHK(hipSetDevice(b->m->device));
   hipStream_t st = (hipStream_t)stream;
-  Mdl md = device_model(b->m);
-  Lay lay;
-  int nwg = d_list ? grid : n;
-  uint32_t* q = nullptr;
-  int slot = 0;
-  if (!d_list && queue_mode() > 0) {
-    int r = resident_workgroups(b->m);
-    if (queue_mode() > 1 && r > queue_mode()) r = queue_mode();
-    if (r > 0 && r < n) {
-      nwg = r;
-      slot = b->qslot++ % MGS_QUEUE_RING;
-      q = b->d_queue + MGS_QHDR * slot;
-      if (sched->yield_every > 0 && d_resume_out) {
-        int rrc = alloc_rings(b, n);
-        if (rrc) return rrc;
-      }
+  a.md = device_model(b->m);
+  a.sc = *sched;
+  a.queue = nullptr;
+  a.ovf_list = a.ovf_count ? a.ovf_count + MGS_LIST_HEADER : nullptr;
+  int nwg = a.list ? list_grid : a.n;
+  if (const int r = a.list ? 0 : queue_grid(b->m, a.n)) {
+    nwg = r;
+    a.queue = b->d_queue + MGS_QHDR * (b->qslot++ % MGS_QUEUE_RING);
+    if (sched->yield_every > 0 && a.resume_out) {
+      int rrc = alloc_rings(b, a.n);
+      if (rrc) return rrc;
     }
   }
-  int lrc = launch_layout(b, nwg, &lay);
+  int lrc = launch_layout(b, nwg, &a.lay);
   if (lrc) return lrc;
   HIPCHK(hipEventRecord(b->e0, st));
-  RolloutArgs a{md, lay, *sched, n, d_qpos_init, d_mocap_quat, d_phase_start, d_phase_target, d_active, d_label,
-                d_fail_step, d_obj_qpos, d_stats, d_vstate, d_state_out, d_list, d_count, d_resume_out, d_resume_in,
-                d_mask_mpos, mask_pred, d_mask_out, q, d_ovf, d_ovf ? d_ovf + MGS_LIST_HEADER : nullptr};
+  const Mdl& md = a.md;
   if (b->m->special_rollout) {
     const int32_t* I = md.I;
     const double* D = md.D;
@@ -620,16 +666,19 @@ int mgs_rollout_device(mgs_batch* b, const mgs_schedule* sched, int n, const dou
                        const double* d_mocap_quat, const double* d_phase_start, const double* d_phase_target,
                        const uint8_t* d_active, uint8_t* d_label, int32_t* d_fail_step, double* d_obj_qpos,
                        int32_t* d_stats, void* stream) {
-  return launch_rollout(b, sched, n, d_qpos_init, d_mocap_quat, d_phase_start, d_phase_target, d_active, d_label,
-                        d_fail_step, d_obj_qpos, d_stats, nullptr, nullptr, stream);
+  RolloutArgs a{};
+  a.n = n; a.qpos_init = d_qpos_init; a.mocap_quat = d_mocap_quat;
+  a.phase_start = d_phase_start; a.phase_target = d_phase_target; a.active = d_active;
+  a.label = d_label; a.fail_step = d_fail_step; a.obj_qpos = d_obj_qpos; a.stats = d_stats;
+  return launch_rollout(b, sched, a, stream);
 }
 
 int mgs_queue_stats(mgs_batch* b, uint64_t* out) {
   if (!b || !out) return fail(MGS_EINVAL, "mgs_queue_stats: null argument%s");
   HIPCHK(hipSetDevice(b->m->device));
   uint32_t h[MGS_QHDR * MGS_QUEUE_RING];
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(h, b->d_queue, sizeof(h), hipMemcpyDeviceToHost));
+  int rc = read_queue_headers(b, h);
+  if (rc) return rc;
   out[0] = out[1] = 0;
   for (int k = 0; k < MGS_QUEUE_RING; k++) {
     out[0] += h[MGS_QHDR * k + 6];
@@ -647,8 +696,8 @@ int mgs_queue_spans(mgs_batch* b, double* out_ms, int cap, int* count, int* over
   b->qslot_drained = b->qslot;
   HIPCHK(hipSetDevice(b->m->device));
   uint32_t h[MGS_QHDR * MGS_QUEUE_RING];
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(h, b->d_queue, sizeof(h), hipMemcpyDeviceToHost));
+  int rc = read_queue_headers(b, h);
+  if (rc) return rc;
   int k = 0;
   for (int i = 0; i < MGS_QUEUE_RING; i++) {
     // oldest first: the slot after the last one handed out
@@ -684,9 +733,12 @@ int mgs_rollout_list_device(mgs_batch* b, const mgs_schedule* sched, int n, int3
                             void* stream) {
   if (!b || !d_count || !d_list || grid < 1 || grid > b->cap)
     return fail(MGS_EINVAL, "mgs_rollout_list_device: bad argument (1 <= grid <= batch capacity)%s");
-  return launch_rollout(b, sched, n, d_qpos_init, d_mocap_quat, d_phase_start, d_phase_target, nullptr, d_label,
-                        d_fail_step, d_obj_qpos, d_stats, nullptr, nullptr, stream, d_list, d_count, grid, nullptr,
-                        d_resume_in);
+  RolloutArgs a{};
+  a.n = n; a.qpos_init = d_qpos_init; a.mocap_quat = d_mocap_quat;
+  a.phase_start = d_phase_start; a.phase_target = d_phase_target;
+  a.label = d_label; a.fail_step = d_fail_step; a.obj_qpos = d_obj_qpos; a.stats = d_stats;
+  a.list = d_list; a.list_count = d_count; a.resume_in = d_resume_in;
+  return launch_rollout(b, sched, a, stream, grid);
 }
 
 int mgs_rollout_resumable_device(mgs_batch* b, const mgs_schedule* sched, int n, const double* d_qpos_init,
@@ -695,9 +747,12 @@ int mgs_rollout_resumable_device(mgs_batch* b, const mgs_schedule* sched, int n,
                                  int32_t* d_fail_step, double* d_obj_qpos, int32_t* d_stats, double* d_resume_out,
                                  int32_t* d_ovf, void* stream) {
   if (!d_resume_out) return fail(MGS_EINVAL, "mgs_rollout_resumable_device: null resume buffer%s");
-  return launch_rollout(b, sched, n, d_qpos_init, d_mocap_quat, d_phase_start, d_phase_target, d_active, d_label,
-                        d_fail_step, d_obj_qpos, d_stats, nullptr, nullptr, stream, nullptr, nullptr, 0,
-                        d_resume_out, nullptr, nullptr, 0, nullptr, d_ovf);
+  RolloutArgs a{};
+  a.n = n; a.qpos_init = d_qpos_init; a.mocap_quat = d_mocap_quat;
+  a.phase_start = d_phase_start; a.phase_target = d_phase_target; a.active = d_active;
+  a.label = d_label; a.fail_step = d_fail_step; a.obj_qpos = d_obj_qpos; a.stats = d_stats;
+  a.resume_out = d_resume_out; a.ovf_count = d_ovf;
+  return launch_rollout(b, sched, a, stream);
 }
 
 int mgs_mask_rollout_device(mgs_batch* b, const mgs_schedule* sched, int n, const double* d_qpos_init,
@@ -708,9 +763,13 @@ int mgs_mask_rollout_device(mgs_batch* b, const mgs_schedule* sched, int n, cons
   if (!d_mocap_pos || !d_free_out) return fail(MGS_EINVAL, "mgs_mask_rollout_device: mocap_pos and free_out are required%s");
   if (predicate < MGS_PRED_ANY_CONTACT || predicate > MGS_PRED_PARTITION_INCL)
     return fail(MGS_EINVAL, "mgs_mask_rollout_device: bad predicate%s");
-  return launch_rollout(b, sched, n, d_qpos_init, d_mocap_quat, d_phase_start, d_phase_target, nullptr, d_label,
-                        d_fail_step, d_obj_qpos, d_stats, nullptr, nullptr, stream, nullptr, nullptr, 0,
-                        d_resume_out, nullptr, d_mocap_pos, predicate, d_free_out, d_ovf);
+  RolloutArgs a{};
+  a.n = n; a.qpos_init = d_qpos_init; a.mocap_quat = d_mocap_quat;
+  a.phase_start = d_phase_start; a.phase_target = d_phase_target;
+  a.label = d_label; a.fail_step = d_fail_step; a.obj_qpos = d_obj_qpos; a.stats = d_stats;
+  a.resume_out = d_resume_out; a.ovf_count = d_ovf;
+  a.mask_mpos = d_mocap_pos; a.mask_pred = predicate; a.mask_out = d_free_out;
+  return launch_rollout(b, sched, a, stream);
 }
 
 int mgs_simulate_device(mgs_batch* b, const mgs_schedule* sched, int n, const double* d_qpos_init,
@@ -720,8 +779,12 @@ int mgs_simulate_device(mgs_batch* b, const mgs_schedule* sched, int n, const do
   mgs_schedule s = *sched;   // no contact checks: a free simulation never stops early
   for (int p = 0; p < MGS_MAX_PHASES; p++) { s.check_every[p] = 0; s.check_at_end[p] = 0; }
   s.enough_stable = 0;       // every state ends "ok" here: nothing to count, nothing to skip
-  return launch_rollout(b, &s, n, d_qpos_init, d_mocap_quat, d_phase_start, d_phase_target, nullptr, b->d_label,
-                        b->d_fail, b->d_objq, d_stats ? d_stats : b->d_stats, d_vstate_init, d_state_out, stream);
+  RolloutArgs a{};
+  a.n = n; a.qpos_init = d_qpos_init; a.mocap_quat = d_mocap_quat;
+  a.phase_start = d_phase_start; a.phase_target = d_phase_target;
+  a.label = b->d_label; a.fail_step = b->d_fail; a.obj_qpos = b->d_objq; a.stats = d_stats ? d_stats : b->d_stats;
+  a.vstate_init = d_vstate_init; a.state_out = d_state_out;
+  return launch_rollout(b, &s, a, stream);
 }
 
 int mgs_simulate(mgs_batch* b, const mgs_schedule* sched, int n, const double* qpos_init,
@@ -734,29 +797,20 @@ int mgs_simulate(mgs_batch* b, const mgs_schedule* sched, int n, const double* q
   const mgs_model_desc& d = b->m->desc;
   int np = sched->nphase;
   HIPCHK(hipSetDevice(b->m->device));
-  double *dv = nullptr, *ds = nullptr;
-  size_t nst = (size_t)n * (d.nq + 2 * d.nv + d.nact);
-  if (hipMalloc(&ds, nst * sizeof(double)) != hipSuccess) return fail(MGS_ENOMEM, "state buffer allocation failed%s");
-  if (vstate_init && hipMalloc(&dv, (size_t)n * (2 * d.nv + d.nact) * sizeof(double)) != hipSuccess) {
-    hipFree(ds);
-    return fail(MGS_ENOMEM, "state buffer allocation failed%s");
-  }
-  int rc = MGS_OK;
-  if (hipMemcpy(b->d_qpos, qpos_init, sizeof(double) * n * d.nq, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(b->d_mquat, mocap_quat, sizeof(double) * n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(b->d_ps, phase_start, sizeof(double) * n * 3 * np, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(b->d_pt, phase_target, sizeof(double) * n * 3 * np, hipMemcpyHostToDevice) != hipSuccess ||
-      (dv && hipMemcpy(dv, vstate_init, (size_t)n * (2 * d.nv + d.nact) * sizeof(double), hipMemcpyHostToDevice) != hipSuccess))
-    rc = fail(MGS_EHIP, "host to device copy failed%s");
-  if (!rc) rc = mgs_simulate_device(b, sched, n, b->d_qpos, dv, b->d_mquat, b->d_ps, b->d_pt, ds, nullptr, nullptr);
-  if (!rc && hipMemcpy(state_out, ds, nst * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-    rc = fail(MGS_EHIP, "device to host copy failed%s");
-  if (!rc && stats &&
-      hipMemcpy(stats, b->d_stats, sizeof(int32_t) * n * MGS_NSTATS, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = fail(MGS_EHIP, "device to host copy failed%s");
-  hipFree(ds);
-  if (dv) hipFree(dv);
-  return rc;
+  const size_t nst = (size_t)n * (d.nq + 2 * d.nv + d.nact);
+  DevBufs bufs;
+  double* ds = bufs.get<double>(nst);
+  double* dv = vstate_init ? upload(bufs, vstate_init, (size_t)n * (2 * d.nv + d.nact)) : nullptr;
+  if (!bufs.ok) return fail(MGS_ENOMEM, "state buffer allocation or upload failed%s");
+  HIPCHK(hipMemcpy(b->d_qpos, qpos_init, sizeof(double) * n * d.nq, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(b->d_mquat, mocap_quat, sizeof(double) * n * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(b->d_ps, phase_start, sizeof(double) * n * 3 * np, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(b->d_pt, phase_target, sizeof(double) * n * 3 * np, hipMemcpyHostToDevice));
+  int rc = mgs_simulate_device(b, sched, n, b->d_qpos, dv, b->d_mquat, b->d_ps, b->d_pt, ds, nullptr, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(state_out, ds, nst * sizeof(double), hipMemcpyDeviceToHost));
+  if (stats) HIPCHK(hipMemcpy(stats, b->d_stats, sizeof(int32_t) * n * MGS_NSTATS, hipMemcpyDeviceToHost));
+  return MGS_OK;
 }
 
 double mgs_last_collision_ms(mgs_batch* b) {
@@ -798,10 +852,18 @@ static int rollout_host(mgs_batch* b, const mgs_schedule* sched, int n, const do
   HIPCHK(hipMemcpy(b->d_pt, phase_target, sizeof(double) * n * 3 * np, hipMemcpyHostToDevice));
   if (resume_in) HIPCHK(hipMemcpy(b->d_resume, resume_in, sizeof(double) * rs * n, hipMemcpyHostToDevice));
   int rc;
-  if (sched->yield_every > 0 && (rc = sync_rotation(b))) return rc;
-  rc = launch_rollout(b, sched, n, b->d_qpos, b->d_mquat, b->d_ps, b->d_pt, nullptr, b->d_label, b->d_fail,
-                          b->d_objq, b->d_stats, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                          out->resume ? b->d_resume : nullptr, resume_in ? b->d_resume : nullptr);
+  // before a synchronous rotating launch: expired spins left by earlier launches
+  // (the device entries', which their callers audit) are acknowledged here and
+  // the rings they may have left dirty are reset, so the check after this launch
+  // counts only its own
+  if (sched->yield_every > 0 && (rc = reset_expired(b))) return rc;
+  RolloutArgs a{};
+  a.n = n; a.qpos_init = b->d_qpos; a.mocap_quat = b->d_mquat;
+  a.phase_start = b->d_ps; a.phase_target = b->d_pt;
+  a.label = b->d_label; a.fail_step = b->d_fail; a.obj_qpos = b->d_objq; a.stats = b->d_stats;
+  a.resume_out = out->resume ? b->d_resume : nullptr;
+  a.resume_in = resume_in ? b->d_resume : nullptr;
+  rc = launch_rollout(b, sched, a, nullptr);
   if (rc) return rc;
   if (sched->yield_every > 0 && (rc = check_rotation(b))) return rc;
   HIPCHK(hipMemcpy(out->label, b->d_label, n, hipMemcpyDeviceToHost));
@@ -827,31 +889,33 @@ int mgs_rollout_resume(mgs_batch* b, const mgs_schedule* sched, int n, const dou
 
 // test hook: device arithmetic on n inputs (out: n*4 = sqrt|x|, x/y, sin, cos)
 int mgs_arith_probe(const double* x, const double* y, int n, double* out) {
-  double *dx, *dy, *dout;
-  HIPCHK(hipMalloc(&dx, sizeof(double) * n));
-  HIPCHK(hipMalloc(&dy, sizeof(double) * n));
-  HIPCHK(hipMalloc(&dout, sizeof(double) * n * 4));
-  HIPCHK(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dy, y, sizeof(double) * n, hipMemcpyHostToDevice));
+  if (n < 0) return fail(MGS_EINVAL, "mgs_arith_probe: negative size%s");
+  if (n == 0) return MGS_OK;
+  if (!x || !y || !out) return fail(MGS_EINVAL, "mgs_arith_probe: null argument%s");
+  DevBufs b;
+  double* dx = upload(b, x, (size_t)n);
+  double* dy = upload(b, y, (size_t)n);
+  double* dout = b.get<double>(4 * (size_t)n);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
   hipLaunchKernelGGL(mgs_arith_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dx, dy, n, dout);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(out, dout, sizeof(double) * n * 4, hipMemcpyDeviceToHost));
-  hipFree(dx); hipFree(dy); hipFree(dout);
   return MGS_OK;
 }
 
 // test hook: pairwise-tree wave reduction, nb blocks of 64 lanes
 int mgs_tree_probe(const double* a, const double* c, int n, int nb, double* out) {
-  double *da, *dc, *dout;
-  HIPCHK(hipMalloc(&da, sizeof(double) * nb * 64));
-  HIPCHK(hipMalloc(&dc, sizeof(double) * nb * 64));
-  HIPCHK(hipMalloc(&dout, sizeof(double) * nb));
-  HIPCHK(hipMemcpy(da, a, sizeof(double) * nb * 64, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dc, c, sizeof(double) * nb * 64, hipMemcpyHostToDevice));
+  if (n < 0 || nb < 0) return fail(MGS_EINVAL, "mgs_tree_probe: negative size%s");
+  if (nb == 0) return MGS_OK;
+  if (!a || !c || !out) return fail(MGS_EINVAL, "mgs_tree_probe: null argument%s");
+  DevBufs b;
+  double* da = upload(b, a, 64 * (size_t)nb);
+  double* dc = upload(b, c, 64 * (size_t)nb);
+  double* dout = b.get<double>((size_t)nb);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
   hipLaunchKernelGGL(mgs_tree_probe_kernel, dim3(nb), dim3(64), 0, 0, da, dc, n, dout);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(out, dout, sizeof(double) * nb, hipMemcpyDeviceToHost));
-  hipFree(da); hipFree(dc); hipFree(dout);
   return MGS_OK;
 }
 
@@ -893,78 +957,28 @@ int mgs_antipodal_contacts(int device, const double* tri, int ntri, int n, const
   if (!tri || !origin || !dir || !u_choice || !out_second || !out_nvalid)
     return fail(MGS_EINVAL, "mgs_antipodal_contacts: null argument%s");
   HIPCHK(hipSetDevice(device));
-  double *dT = nullptr, *dO = nullptr, *dD = nullptr, *dU = nullptr, *dS = nullptr;
-  int32_t* dN = nullptr;
-  size_t nt = (size_t)(ntri > 0 ? ntri : 1) * 9;
-  bool ok = hipMalloc(&dT, nt * sizeof(double)) == hipSuccess && hipMalloc(&dO, 3 * n * sizeof(double)) == hipSuccess &&
-            hipMalloc(&dD, 3 * n * sizeof(double)) == hipSuccess && hipMalloc(&dU, n * sizeof(double)) == hipSuccess &&
-            hipMalloc(&dS, 3 * n * sizeof(double)) == hipSuccess && hipMalloc(&dN, n * sizeof(int32_t)) == hipSuccess;
-  int rc = MGS_OK;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (!ok) {
-    rc = fail(MGS_ENOMEM, "device allocation failed%s");
-  } else {
-    if (ntri > 0) hipMemcpy(dT, tri, (size_t)ntri * 9 * sizeof(double), hipMemcpyHostToDevice);
-    hipMemcpy(dO, origin, 3 * n * sizeof(double), hipMemcpyHostToDevice);
-    hipMemcpy(dD, dir, 3 * n * sizeof(double), hipMemcpyHostToDevice);
-    hipMemcpy(dU, u_choice, n * sizeof(double), hipMemcpyHostToDevice);
-    hipEventCreate(&e0);
-    hipEventCreate(&e1);
-    hipEventRecord(e0, nullptr);
-    hipLaunchKernelGGL(mgs_antipodal_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, dT, ntri, n, dO, dD, dU,
-                       eps, dS, dN);
-    hipEventRecord(e1, nullptr);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    if (e != hipSuccess) {
-      rc = fail(MGS_EHIP, "HIP error: %s", hipGetErrorString(e));
-    } else {
-      float ms = 0.f;
-      hipEventElapsedTime(&ms, e0, e1);
-      if (kernel_ms) *kernel_ms = ms;
-      hipMemcpy(out_second, dS, 3 * n * sizeof(double), hipMemcpyDeviceToHost);
-      hipMemcpy(out_nvalid, dN, n * sizeof(int32_t), hipMemcpyDeviceToHost);
-    }
+  const size_t nn = (size_t)n;
+  DevBufs b;
+  double* dT = upload(b, tri, 9 * (size_t)ntri);
+  double* dO = upload(b, origin, 3 * nn);
+  double* dD = upload(b, dir, 3 * nn);
+  double* dU = upload(b, u_choice, nn);
+  double* dS = b.get<double>(3 * nn);
+  int32_t* dN = b.get<int32_t>(nn);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
+  EvTimer t;
+  hipLaunchKernelGGL(mgs_antipodal_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, dT, ntri, n, dO, dD, dU,
+                     eps, dS, dN);
+  int rc = t.finish(kernel_ms);
+  if (rc == MGS_OK) {
+    HIPCHK(hipMemcpy(out_second, dS, 3 * nn * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_nvalid, dN, nn * sizeof(int32_t), hipMemcpyDeviceToHost));
   }
-  if (e0) hipEventDestroy(e0);
-  if (e1) hipEventDestroy(e1);
-  hipFree(dT); hipFree(dO); hipFree(dD); hipFree(dU); hipFree(dS); hipFree(dN);
   return rc;
 }
 
 // ---------------------------------------------------------------------------
 // contact-based dexterous-hand sampler (csrc/mgs_contact.hip)
-}  // extern "C"
-namespace {
-struct DevBufs {
-  std::vector<void*> p;
-  bool ok = true;
-  template <class T>
-  T* get(size_t n) {
-    void* q = nullptr;
-    if (hipMalloc(&q, (n > 0 ? n : 1) * sizeof(T)) != hipSuccess) { ok = false; return nullptr; }
-    p.push_back(q);
-    return (T*)q;
-  }
-  ~DevBufs() { for (void* q : p) hipFree(q); }
-};
-struct EvTimer {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  EvTimer() { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, nullptr); }
-  int finish(double* ms) {
-    hipEventRecord(e1, nullptr);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    if (e != hipSuccess) return fail(MGS_EHIP, "HIP error: %s", hipGetErrorString(e));
-    float f = 0.f;
-    hipEventElapsedTime(&f, e0, e1);
-    if (ms) *ms = f;
-    return MGS_OK;
-  }
-  ~EvTimer() { hipEventDestroy(e0); hipEventDestroy(e1); }
-};
-}  // namespace
-extern "C" {
 
 int mgs_kin_desc_size(void) { return (int)sizeof(mgs_kin_desc); }
 
@@ -1093,7 +1107,7 @@ const char* scan_scene_error(const mgs_scan_scene* s) {
     if (t == MGS_SCAN_CAPSULE || t == MGS_SCAN_CYLINDER) {
       const double r = s->draw_size[3 * (size_t)d], h = s->draw_size[3 * (size_t)d + 1];
       // written so that a NaN fails: radius finite and > 0, half-length finite and >= 0
-      if (!(r > 0.0 && r <= 1.7976931348623157e308 && h >= 0.0 && h <= 1.7976931348623157e308)) {
+      if (!(r > 0.0 && is_finite(r) && h >= 0.0 && is_finite(h))) {
         static thread_local char msg[96];
         snprintf(msg, sizeof(msg), "drawable %d: a %s needs a finite radius > 0 and a finite half-length >= 0", d,
                  t == MGS_SCAN_CAPSULE ? "capsule" : "cylinder");
@@ -1103,32 +1117,46 @@ const char* scan_scene_error(const mgs_scan_scene* s) {
   }
   return "";
 }
-template <class T>
-T* scan_upload(DevBufs& b, const T* src, size_t n) {
-  T* d = b.get<T>(n);
-  if (d && n > 0 && hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) b.ok = false;
-  return d;
-}
 // a checked scene's arrays on the device
 ScanDev scan_upload_scene(DevBufs& b, const mgs_scan_scene* scene) {
   const size_t nd = (size_t)scene->ndraw, nm = (size_t)scene->nmesh, nn = (size_t)scene->nnode, nt = (size_t)scene->ntri;
   ScanDev S;
   S.ndraw = scene->ndraw;
-  S.dtype = scan_upload(b, scene->draw_type, nd);
-  S.did = scan_upload(b, scene->draw_id, nd);
-  S.dmesh = scan_upload(b, scene->draw_mesh, nd);
-  S.dpos = scan_upload(b, scene->draw_pos, 3 * nd);
-  S.drot = scan_upload(b, scene->draw_rot, 9 * nd);
-  S.dsize = scan_upload(b, scene->draw_size, 3 * nd);
-  S.mnode0 = scan_upload(b, scene->mesh_node0, nm ? nm + 1 : 0);
-  S.mtri0 = scan_upload(b, scene->mesh_tri0, nm ? nm + 1 : 0);
-  S.nbox = scan_upload(b, scene->node_box, 6 * nn);
-  S.nskip = scan_upload(b, scene->node_skip, nn);
-  S.nfirst = scan_upload(b, scene->node_first, nn);
-  S.ncount = scan_upload(b, scene->node_count, nn);
-  S.tri = scan_upload(b, scene->tri, 9 * nt);
-  S.face = scan_upload(b, scene->tri_face, nt);
+  S.dtype = upload(b, scene->draw_type, nd);
+  S.did = upload(b, scene->draw_id, nd);
+  S.dmesh = upload(b, scene->draw_mesh, nd);
+  S.dpos = upload(b, scene->draw_pos, 3 * nd);
+  S.drot = upload(b, scene->draw_rot, 9 * nd);
+  S.dsize = upload(b, scene->draw_size, 3 * nd);
+  S.mnode0 = upload(b, scene->mesh_node0, nm ? nm + 1 : 0);
+  S.mtri0 = upload(b, scene->mesh_tri0, nm ? nm + 1 : 0);
+  S.nbox = upload(b, scene->node_box, 6 * nn);
+  S.nskip = upload(b, scene->node_skip, nn);
+  S.nfirst = upload(b, scene->node_first, nn);
+  S.ncount = upload(b, scene->node_count, nn);
+  S.tri = upload(b, scene->tri, 9 * nt);
+  S.face = upload(b, scene->tri_face, nt);
   return S;
+}
+// the view arguments of the entry named `entry` (a render's views are its
+// grid's z: at most 65535); *npix = the pixels of all views
+int check_views(const char* entry, int nview, int width, int height, double fx, double fy, bool render, size_t* npix) {
+  if (nview < 0 || width < 0 || height < 0) return fail(MGS_EINVAL, "%s: negative size", entry);
+  if (render && nview > 65535) return fail(MGS_EINVAL, "%s: at most 65535 views per call", entry);
+  if (!(fx > 0.0) || !(fy > 0.0)) return fail(MGS_EINVAL, "%s: focal lengths must be positive", entry);
+  *npix = (size_t)nview * (size_t)width * (size_t)height;
+  if (*npix > (size_t)1 << 30) return fail(MGS_EINVAL, "%s: more than 2^30 pixels", entry);
+  return MGS_OK;
+}
+// the region mgs_scan_points keeps when the caller names none (the reference's)
+const double ref_region[6] = {-0.25, -0.25, -0.01, 0.25, 0.25, 1.0};
+// depth, segmentation, face id and triangle-test count of every pixel, on the null stream
+void launch_scan_render(const ScanDev& S, const double* dP, const double* dR, int nview, int width, int height,
+                        double fx, double fy, double cx, double cy, double* oD, int32_t* oS, int32_t* oT, int32_t* oN) {
+  hipLaunchKernelGGL(mgs_scan_kernel,
+                     dim3((width + MGS_SCAN_TILE - 1) / MGS_SCAN_TILE, (height + MGS_SCAN_TILE - 1) / MGS_SCAN_TILE, nview),
+                     dim3(MGS_SCAN_TILE * MGS_SCAN_TILE), 0, nullptr, S, dP, dR, width, height, fx, fy, cx, cy, oD, oS,
+                     oT, oN);
 }
 }  // namespace
 extern "C" {
@@ -1137,31 +1165,25 @@ int mgs_scan_render(int device, const mgs_scan_scene* scene, int nview, const do
                     const double* cam_rot, int width, int height, double fx, double fy, double cx, double cy,
                     double* out_depth, int32_t* out_seg, int32_t* out_tri, int32_t* out_ntest, double* kernel_ms) {
   if (!scene) return fail(MGS_EINVAL, "mgs_scan_render: null scene%s");
-  if (nview < 0 || width < 0 || height < 0) return fail(MGS_EINVAL, "mgs_scan_render: negative size%s");
-  if (nview > 65535) return fail(MGS_EINVAL, "mgs_scan_render: at most 65535 views per call%s");
-  if (!(fx > 0.0) || !(fy > 0.0)) return fail(MGS_EINVAL, "mgs_scan_render: focal lengths must be positive%s");
+  size_t n = 0;
+  if (int rc = check_views("mgs_scan_render", nview, width, height, fx, fy, true, &n)) return rc;
   const char* bad = scan_scene_error(scene);
   if (bad[0]) return fail(MGS_EINVAL, "mgs_scan_render: scene: %s", bad);
-  const size_t n = (size_t)nview * (size_t)width * (size_t)height;
-  if (n > (size_t)1 << 30) return fail(MGS_EINVAL, "mgs_scan_render: more than 2^30 pixels%s");
   if (n == 0) return MGS_OK;
   if (!cam_pos || !cam_rot || !out_depth || !out_seg || !out_tri)
     return fail(MGS_EINVAL, "mgs_scan_render: null argument%s");
   HIPCHK(hipSetDevice(device));
   DevBufs b;
   ScanDev S = scan_upload_scene(b, scene);
-  double* dP = scan_upload(b, cam_pos, 3 * (size_t)nview);
-  double* dR = scan_upload(b, cam_rot, 9 * (size_t)nview);
+  double* dP = upload(b, cam_pos, 3 * (size_t)nview);
+  double* dR = upload(b, cam_rot, 9 * (size_t)nview);
   double* oD = b.get<double>(n);
   int32_t* oS = b.get<int32_t>(n);
   int32_t* oT = b.get<int32_t>(n);
   int32_t* oN = b.get<int32_t>(n);
   if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
   EvTimer t;
-  hipLaunchKernelGGL(mgs_scan_kernel,
-                     dim3((width + MGS_SCAN_TILE - 1) / MGS_SCAN_TILE, (height + MGS_SCAN_TILE - 1) / MGS_SCAN_TILE, nview),
-                     dim3(MGS_SCAN_TILE * MGS_SCAN_TILE), 0, nullptr, S, dP, dR, width, height, fx, fy, cx, cy, oD, oS,
-                     oT, oN);
+  launch_scan_render(S, dP, dR, nview, width, height, fx, fy, cx, cy, oD, oS, oT, oN);
   int rc = t.finish(kernel_ms);
   if (rc == MGS_OK) {
     HIPCHK(hipMemcpy(out_depth, oD, n * sizeof(double), hipMemcpyDeviceToHost));
@@ -1175,21 +1197,18 @@ int mgs_scan_render(int device, const mgs_scan_scene* scene, int nview, const do
 int mgs_scan_points(int device, int nview, int width, int height, const double* depth, const int32_t* seg,
                     const double* extrinsics, double fx, double fy, double cx, double cy, int erode_iters,
                     const double* region, double* out_points, uint8_t* out_keep, double* kernel_ms) {
-  if (nview < 0 || width < 0 || height < 0) return fail(MGS_EINVAL, "mgs_scan_points: negative size%s");
+  size_t n = 0;
+  if (int rc = check_views("mgs_scan_points", nview, width, height, fx, fy, false, &n)) return rc;
   if (erode_iters < 0 || erode_iters > 64) return fail(MGS_EINVAL, "mgs_scan_points: erode_iters must be 0 .. 64%s");
-  if (!(fx > 0.0) || !(fy > 0.0)) return fail(MGS_EINVAL, "mgs_scan_points: focal lengths must be positive%s");
-  const size_t n = (size_t)nview * (size_t)width * (size_t)height;
-  if (n > (size_t)1 << 30) return fail(MGS_EINVAL, "mgs_scan_points: more than 2^30 pixels%s");
   if (n == 0) return MGS_OK;
   if (!depth || !seg || !extrinsics || !out_points || !out_keep)
     return fail(MGS_EINVAL, "mgs_scan_points: null argument%s");
-  static const double ref_region[6] = {-0.25, -0.25, -0.01, 0.25, 0.25, 1.0};
   const double* rg = region ? region : ref_region;
   HIPCHK(hipSetDevice(device));
   DevBufs b;
-  double* dD = scan_upload(b, depth, n);
-  int32_t* dS = scan_upload(b, seg, n);
-  double* dE = scan_upload(b, extrinsics, 16 * (size_t)nview);
+  double* dD = upload(b, depth, n);
+  int32_t* dS = upload(b, seg, n);
+  double* dE = upload(b, extrinsics, 16 * (size_t)nview);
   double* oP = b.get<double>(3 * n);
   uint8_t* oK = b.get<uint8_t>(n);
   if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
@@ -1332,7 +1351,7 @@ int cloud_fps_dev(DevBufs& b, const double* dX, int n, int k, double bucket_size
   double ext[3];
   for (int a = 0; a < 3; a++) {
     ext[a] = h.hi[a] - h.lo[a];
-    if (!(ext[a] <= 1.7976931348623157e308)) return fail(MGS_EINVAL, "cloud pick: the points' extent is not finite%s");
+    if (!is_finite(ext[a])) return fail(MGS_EINVAL, "cloud pick: the points' extent is not finite%s");
   }
   CloudGrid G;
   double side = bucket_size, d[3];
@@ -1369,7 +1388,7 @@ int cloud_fps_dev(DevBufs& b, const double* dX, int n, int k, double bucket_size
   return MGS_OK;
 }
 
-bool cloud_size_ok(double v) { return v > 0.0 && v <= 1.7976931348623157e308; }
+bool cloud_size_ok(double v) { return v > 0.0 && is_finite(v); }
 
 struct CloudEvents {
   hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1391,16 +1410,15 @@ int mgs_scan_voxels(int device, int n, const double* points, const uint8_t* keep
   for (size_t j = 0; j < (size_t)n; j++) {
     if (keep && !keep[j]) continue;
     for (int a = 0; a < 3; a++)
-      if (!(fabs(points[3 * j + a]) <= 1.7976931348623157e308))
-        return fail(MGS_EINVAL, "mgs_scan_voxels: a kept point is not finite%s");
+      if (!is_finite(points[3 * j + a])) return fail(MGS_EINVAL, "mgs_scan_voxels: a kept point is not finite%s");
   }
   if (n == 0) { *out_nvox = 0; return MGS_OK; }
   HIPCHK(hipSetDevice(device));
   DevBufs b;
   const size_t nn = (size_t)n;
-  double* dX = scan_upload(b, points, 3 * nn);
-  uint8_t* dK = keep ? scan_upload(b, keep, nn) : nullptr;
-  float* dF = nfeat > 0 ? scan_upload(b, features, (size_t)nfeat * nn) : nullptr;
+  double* dX = upload(b, points, 3 * nn);
+  uint8_t* dK = keep ? upload(b, keep, nn) : nullptr;
+  float* dF = nfeat > 0 ? upload(b, features, (size_t)nfeat * nn) : nullptr;
   if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
   EvTimer t;
   CloudVox V;
@@ -1426,14 +1444,14 @@ int mgs_scan_fps(int device, const double* points, int n, int k, double bucket_s
   if (k > 0 && (!points || !out_idx)) return fail(MGS_EINVAL, "mgs_scan_fps: null argument%s");
   if (k > 0)
     for (size_t j = 0; j < 3 * (size_t)n; j++)
-      if (!(fabs(points[j]) <= 1.7976931348623157e308)) return fail(MGS_EINVAL, "mgs_scan_fps: a point is not finite%s");
+      if (!is_finite(points[j])) return fail(MGS_EINVAL, "mgs_scan_fps: a point is not finite%s");
   if (k == 0) {
     if (out_nevals) *out_nevals = 0;
     return MGS_OK;
   }
   HIPCHK(hipSetDevice(device));
   DevBufs b;
-  double* dX = scan_upload(b, points, 3 * (size_t)n);
+  double* dX = upload(b, points, 3 * (size_t)n);
   int32_t* dO = b.get<int32_t>((size_t)k);
   cloud_u64* dEv = b.get<cloud_u64>(1);
   if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
@@ -1455,11 +1473,10 @@ int mgs_scan_cloud(int device, const mgs_scan_scene* scene, int nview, const dou
                    const float* colors, int ncolor, double voxel_size, int num_points, float* out_points,
                    float* out_colors, int32_t* out_n, int64_t* out_stats, double* stage_ms) {
   if (!scene) return fail(MGS_EINVAL, "mgs_scan_cloud: null scene%s");
-  if (nview < 0 || width < 0 || height < 0 || num_points < 0 || ncolor < 0)
-    return fail(MGS_EINVAL, "mgs_scan_cloud: negative size%s");
-  if (nview > 65535) return fail(MGS_EINVAL, "mgs_scan_cloud: at most 65535 views per call%s");
-  if (!(fx > 0.0) || !(fy > 0.0) || !(pfx > 0.0) || !(pfy > 0.0))
-    return fail(MGS_EINVAL, "mgs_scan_cloud: focal lengths must be positive%s");
+  size_t n = 0;
+  if (int rc = check_views("mgs_scan_cloud", nview, width, height, fx, fy, true, &n)) return rc;
+  if (num_points < 0 || ncolor < 0) return fail(MGS_EINVAL, "mgs_scan_cloud: negative size%s");
+  if (!(pfx > 0.0) || !(pfy > 0.0)) return fail(MGS_EINVAL, "mgs_scan_cloud: focal lengths must be positive%s");
   if (erode_iters < 0 || erode_iters > 64) return fail(MGS_EINVAL, "mgs_scan_cloud: erode_iters must be 0 .. 64%s");
   if (!cloud_size_ok(voxel_size)) return fail(MGS_EINVAL, "mgs_scan_cloud: voxel_size must be positive and finite%s");
   const char* bad = scan_scene_error(scene);
@@ -1467,23 +1484,20 @@ int mgs_scan_cloud(int device, const mgs_scan_scene* scene, int nview, const dou
   for (int d = 0; d < scene->ndraw; d++)
     if (scene->draw_id[d] < 0 || scene->draw_id[d] >= ncolor)
       return fail(MGS_EINVAL, "mgs_scan_cloud: a draw_id has no row of colors%s");
-  const size_t n = (size_t)nview * (size_t)width * (size_t)height;
-  if (n > (size_t)1 << 30) return fail(MGS_EINVAL, "mgs_scan_cloud: more than 2^30 pixels%s");
   if (!out_n || (ncolor > 0 && !colors) || (num_points > 0 && (!out_points || !out_colors)) ||
       (n > 0 && (!cam_pos || !cam_rot || !extrinsics)))
     return fail(MGS_EINVAL, "mgs_scan_cloud: null argument%s");
   if (out_stats) for (int i = 0; i < 8; i++) out_stats[i] = 0;
   if (stage_ms) for (int i = 0; i < 4; i++) stage_ms[i] = 0.0;
   if (n == 0) { *out_n = 0; return MGS_OK; }
-  static const double ref_region[6] = {-0.25, -0.25, -0.01, 0.25, 0.25, 1.0};
   const double* rg = region ? region : ref_region;
   HIPCHK(hipSetDevice(device));
   DevBufs b;
   ScanDev S = scan_upload_scene(b, scene);
-  double* dCP = scan_upload(b, cam_pos, 3 * (size_t)nview);
-  double* dCR = scan_upload(b, cam_rot, 9 * (size_t)nview);
-  double* dE = scan_upload(b, extrinsics, 16 * (size_t)nview);
-  float* dCol = scan_upload(b, colors, 3 * (size_t)ncolor);
+  double* dCP = upload(b, cam_pos, 3 * (size_t)nview);
+  double* dCR = upload(b, cam_rot, 9 * (size_t)nview);
+  double* dE = upload(b, extrinsics, 16 * (size_t)nview);
+  float* dCol = upload(b, colors, 3 * (size_t)ncolor);
   double* dD = b.get<double>(n);
   double* dD32 = b.get<double>(n);
   int32_t* dS = b.get<int32_t>(n);
@@ -1495,10 +1509,7 @@ int mgs_scan_cloud(int device, const mgs_scan_scene* scene, int nview, const dou
   CloudEvents ev;
   const unsigned pix_blocks = (unsigned)((n + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK);
   hipEventRecord(ev.e[0], nullptr);
-  hipLaunchKernelGGL(mgs_scan_kernel,
-                     dim3((width + MGS_SCAN_TILE - 1) / MGS_SCAN_TILE, (height + MGS_SCAN_TILE - 1) / MGS_SCAN_TILE, nview),
-                     dim3(MGS_SCAN_TILE * MGS_SCAN_TILE), 0, nullptr, S, dCP, dCR, width, height, fx, fy, cx, cy, dD, dS,
-                     dT, dN);
+  launch_scan_render(S, dCP, dCR, nview, width, height, fx, fy, cx, cy, dD, dS, dT, dN);
   hipEventRecord(ev.e[1], nullptr);
   hipLaunchKernelGGL(cloud_round_f32_kernel, dim3(pix_blocks), dim3(MGS_CLOUD_BLOCK), 0, nullptr, dD, n, dD32);
   hipLaunchKernelGGL(mgs_scan_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, nview, width,
@@ -1578,15 +1589,9 @@ int mgs_model_lds_bytes(const mgs_model_desc* desc, int64_t* out_bytes) {
 int mgs_model_layout(const mgs_model_desc* desc, int32_t* out, int cap, int32_t* nwords) {
   if (!desc || !out || !nwords) return fail(MGS_EINVAL, "mgs_model_layout: null argument%s");
   size_t b = 0;
-  Lay l = make_layout(*desc, &b);
-  int32_t w[L_COUNT + U_COUNT + 4];
-  int k = 0;
-  for (int i = 0; i < L_COUNT; i++) w[k++] = l.o[i];
-  for (int i = 0; i < U_COUNT; i++) w[k++] = l.u[i];
-  w[k++] = l.ncon_max; w[k++] = l.nefc_max; w[k++] = l.nv; w[k++] = l.total_doubles;
-  if (cap < k) return fail(MGS_EINVAL, "mgs_model_layout: output too small%s");
-  for (int i = 0; i < k; i++) out[i] = w[i];
-  *nwords = k;
+  if (cap < LAYOUT_WORDS) return fail(MGS_EINVAL, "mgs_model_layout: output too small%s");
+  layout_words(make_layout(*desc, &b), out);
+  *nwords = LAYOUT_WORDS;
   return MGS_OK;
 }
 
@@ -1599,36 +1604,29 @@ int mgs_model_attach_special(mgs_model* m, const char* path) {
   if (hipModuleLoad(&mod, path) != hipSuccess) return fail(MGS_EINVAL, "cannot load code object %s", path);
   // the object's baked ABI version, description and layout must be this model's
   auto check = [&]() -> int {
-    hipDeviceptr_t p;
-    size_t sz = 0;
-    int abi = 0, rpl = 0;
+    // a global of a code object, read into *v when it has the expected size
+    auto module_global = [](hipModule_t md, const char* name, void* v, size_t bytes) {
+      hipDeviceptr_t p;
+      size_t sz = 0;
+      return hipModuleGetGlobal(&p, &sz, md, name) == hipSuccess && sz == bytes &&
+             hipMemcpyDtoH(v, p, bytes) == hipSuccess;
+    };
+    auto module_int = [&](hipModule_t md, const char* name, int* v) { return module_global(md, name, v, sizeof(int)); };
+    int abi = 0, rpl = 0, mxd = 0, mxnv = 0;
     mgs_model_desc dsc;
-    int32_t w[L_COUNT + U_COUNT + 4];
-    if (hipModuleGetGlobal(&p, &sz, mod, "mgs_special_abi") != hipSuccess || sz != sizeof(int) ||
-        hipMemcpyDtoH(&abi, p, sizeof(int)) != hipSuccess || abi != MGS_ABI_VERSION)
+    int32_t w[LAYOUT_WORDS], mine[LAYOUT_WORDS];
+    if (!module_int(mod, "mgs_special_abi", &abi) || abi != MGS_ABI_VERSION)
       return fail(MGS_EINVAL, "code object %s is of another ABI version", path);
-    if (hipModuleGetGlobal(&p, &sz, mod, "mgs_special_rows_per_lane") != hipSuccess || sz != sizeof(int) ||
-        hipMemcpyDtoH(&rpl, p, sizeof(int)) != hipSuccess || rpl != MGS_RPL)
+    if (!module_int(mod, "mgs_special_rows_per_lane", &rpl) || rpl != MGS_RPL)
       return fail(MGS_EINVAL, "code object %s is of the other library flavour (rows per lane)", path);
-    int mxd = 0;
-    if (hipModuleGetGlobal(&p, &sz, mod, "mgs_special_maxdim") != hipSuccess || sz != sizeof(int) ||
-        hipMemcpyDtoH(&mxd, p, sizeof(int)) != hipSuccess || mxd != layout_maxdim(m->desc))
+    if (!module_int(mod, "mgs_special_maxdim", &mxd) || mxd != layout_maxdim(m->desc))
       return fail(MGS_EINVAL, "code object %s was built for another contact dimension (MGS_MAXDIM)", path);
-    int mxnv = 0;
-    if (hipModuleGetGlobal(&p, &sz, mod, "mgs_special_max_nv") != hipSuccess || sz != sizeof(int) ||
-        hipMemcpyDtoH(&mxnv, p, sizeof(int)) != hipSuccess || mxnv < m->desc.nv)
+    if (!module_int(mod, "mgs_special_max_nv", &mxnv) || mxnv < m->desc.nv)
       return fail(MGS_EINVAL, "code object %s holds fewer dofs per lane than the model needs (MGS_DPL)", path);
-    if (hipModuleGetGlobal(&p, &sz, mod, "mgs_special_desc") != hipSuccess || sz != sizeof(dsc) ||
-        hipMemcpyDtoH(&dsc, p, sizeof(dsc)) != hipSuccess || memcmp(&dsc, &m->desc, sizeof(dsc)) != 0)
+    if (!module_global(mod, "mgs_special_desc", &dsc, sizeof(dsc)) || memcmp(&dsc, &m->desc, sizeof(dsc)) != 0)
       return fail(MGS_EINVAL, "code object %s was specialised for another model description", path);
-    const Lay& l = m->lay;
-    int k = 0;
-    int32_t mine[L_COUNT + U_COUNT + 4];
-    for (int i = 0; i < L_COUNT; i++) mine[k++] = l.o[i];
-    for (int i = 0; i < U_COUNT; i++) mine[k++] = l.u[i];
-    mine[k++] = l.ncon_max; mine[k++] = l.nefc_max; mine[k++] = l.nv; mine[k++] = l.total_doubles;
-    if (hipModuleGetGlobal(&p, &sz, mod, "mgs_special_words") != hipSuccess || sz != sizeof(w) ||
-        hipMemcpyDtoH(w, p, sizeof(w)) != hipSuccess || memcmp(w, mine, sizeof(w)) != 0)
+    layout_words(m->lay, mine);
+    if (!module_global(mod, "mgs_special_words", w, sizeof(w)) || memcmp(w, mine, sizeof(w)) != 0)
       return fail(MGS_EINVAL, "code object %s was specialised for another LDS layout", path);
     return MGS_OK;
   };
@@ -1661,10 +1659,8 @@ int mgs_model_attach_special(mgs_model* m, const char* path) {
 int mgs_rollout_grid(mgs_batch* b, int n) {
   if (!b || n < 0) return fail(MGS_EINVAL, "mgs_rollout_grid: bad argument%s");
   if (hipSetDevice(b->m->device) != hipSuccess) return fail(MGS_EHIP, "mgs_rollout_grid: hipSetDevice failed%s");
-  if (queue_mode() == 0) return n;
-  int r = resident_workgroups(b->m);
-  if (queue_mode() > 1 && r > queue_mode()) r = queue_mode();
-  return (r > 0 && r < n) ? r : n;
+  const int r = queue_grid(b->m, n);
+  return r ? r : n;
 }
 
 int mgs_rollout_queue(int mode) {

@@ -528,12 +528,17 @@ class Engine:
         return self.lib.mgs_last_kernel_ms(self._batch)
 
 
-def antipodal_contacts(tri, origin, direction, u_choice, eps, device=0):
-    """GPU ray casting of the antipodal sampler (mgs_antipodal_contacts):
-    returns (second contact (n,3), valid-hit count (n,), kernel ms)."""
+def _device_lib(device):
     L = load_library()
     if L.mgs_device_count() <= device:
         raise EngineError("no HIP device visible for the MI355X engine")
+    return L
+
+
+def antipodal_contacts(tri, origin, direction, u_choice, eps, device=0):
+    """GPU ray casting of the antipodal sampler (mgs_antipodal_contacts):
+    returns (second contact (n,3), valid-hit count (n,), kernel ms)."""
+    L = _device_lib(device)
     tri = np.ascontiguousarray(tri, np.float64).reshape(-1, 9)
     o = np.ascontiguousarray(origin, np.float64).reshape(-1, 3)
     d = np.ascontiguousarray(direction, np.float64).reshape(-1, 3)
@@ -547,13 +552,6 @@ def antipodal_contacts(tri, origin, direction, u_choice, eps, device=0):
                                     ptr(sec, ctypes.c_double), ptr(cnt, ctypes.c_int32), ctypes.byref(ms)),
            "mgs_antipodal_contacts", L)
     return sec, cnt, ms.value
-
-
-def _device_lib(device):
-    L = load_library()
-    if L.mgs_device_count() <= device:
-        raise EngineError("no HIP device visible for the MI355X engine")
-    return L
 
 
 def contact_fps(points, k, device=0):
