@@ -538,12 +538,14 @@ def _device_lib(device):
 def antipodal_contacts(tri, origin, direction, u_choice, eps, device=0):
     """GPU ray casting of the antipodal sampler (mgs_antipodal_contacts):
     returns (second contact (n,3), valid-hit count (n,), kernel ms)."""
-    L = _device_lib(device)
     tri = np.ascontiguousarray(tri, np.float64).reshape(-1, 9)
     o = np.ascontiguousarray(origin, np.float64).reshape(-1, 3)
     d = np.ascontiguousarray(direction, np.float64).reshape(-1, 3)
     u = np.ascontiguousarray(u_choice, np.float64).reshape(-1)
     n = len(o)
+    if len(d) != n or len(u) != n:
+        raise ValueError(f"antipodal_contacts: {n} origins, {len(d)} directions, {len(u)} choice uniforms")
+    L = _device_lib(device)
     sec = np.zeros((n, 3))
     cnt = np.zeros(n, np.int32)
     ms = ctypes.c_double(0.0)

@@ -13,7 +13,17 @@ fixtures for it.  What is pinned instead:
     scale(-lr)) against a numpy transcription on a one-parameter problem;
   * farthest-point sampling, the seed neighbourhoods and the initial
     permutation assignment against direct numpy restatements;
-  * GPU == oracle bit for bit (-m gpu).
+  * GPU == oracle bit for bit (-m gpu);
+  * in tests/test_contact_truth.py, against tests/sampler_truth.py: the seeds'
+    nearest neighbour and picks (splitmix64 keys, their order, the strict
+    radius) over sizes around the tile of 256, fewer seeds than tips,
+    duplicate seeds and keys with the top bit set; the fit after 0, 1, 5 and
+    20 steps against a torch float64 transcription of the reference's formulas
+    with autograd's gradient, within 64 times that truth's own sensitivity;
+  * in tests/test_contact_edges_gpu.py (-m gpu): the three kernels against the
+    same truths and the oracle at their block and tile edges
+    (farthest-point pick at 1023..2049 points and with every pick tied, the
+    fit at 1..130 candidates and 0, 1 and 150 steps).
 """
 from itertools import permutations
 

@@ -5,7 +5,15 @@ its CPU restatement (oracle_antipodal_contacts).
 CPU: analytic ray-box hits, the choice rule over several hits, Wood's von
 Mises-Fisher sampler's mean resultant (coth k - 1/k), the reference's
 denormalisation.  GPU: bit-exact against the oracle on real meshes, and the
-whole generate_grasps_device batch against a host restatement."""
+whole generate_grasps_device batch against a host restatement.
+
+The ray caster's independent truths are in tests/sampler_truth.py: a numpy
+restatement in the kernel's order of operations and an exact one in rational
+arithmetic.  tests/test_sampler_truth.py holds the oracle to them (hits in
+several tiles out of depth order, rays on edges, corners and faces of a dyadic
+box, three eps values, the choice uniform at every slot edge),
+tests/test_sampler_edges_gpu.py the kernel (-m gpu), at ray and triangle counts
+around 256 and with no triangle at all."""
 import numpy as np
 import pytest
 
