@@ -808,6 +808,62 @@ int mgs_scan_cloud(int device, const mgs_scan_scene* scene, int nview, const dou
                    const float* colors, int ncolor, double voxel_size, int num_points, float* out_points,
                    float* out_colors, int32_t* out_n, int64_t* out_stats, double* stage_ms);
 
+/* ---------------------------------------------------------------------------
+ * Posed gripper cloud (csrc/mgs_pose.hip): the cloud of a scanned gripper at
+ * each of nbatch joint states -- what the reference's kinematic_pcd_transform
+ * (mgs/sampler/kin/base.py:34-77) gives for per-joint masks that nest along
+ * the tree -- optionally placed at nbatch grasp poses.  Additive entries (the
+ * ABI version stays).  Every argument is checked before anything is launched
+ * or written.
+ *
+ * The tree: link i (0 <= i < nlink) hangs from link parent[i] < i, or from the
+ * base (-1).  kin_tf[i]: the parent's link frame -> link i's rest frame, unit
+ * quaternion wxyz + xyz (the caller normalises: the inverse below is the
+ * conjugate); joint_tf[i]: prismatic direction and revolute axis in that
+ * frame; theta_scan: the joint values the cloud was scanned at.  With
+ *   J_i(t) = (quaternion_from_axis_angle(axis_i, t), direction_i t)
+ *            (an axis of norm 0: the identity quaternion, no division),
+ *   W_i(theta) = W_parent(i)(theta) o kin_tf[i] o J_i(theta_i),  W_base = identity,
+ * a point of link k = point_link[p] - 1 (point_link 0: the base) moves by
+ *   M_k = W_k(theta_b) o W_k(theta_scan)^-1  as a 3 x 4 matrix (MuJoCo's
+ * quat2mat), pre-multiplied by base[b] when base is given, and
+ *   out[b][p][r] = ((M[r][0] x + M[r][1] y) + M[r][2] z) + M[r][3]
+ * in f64 without contraction, stored as f64 or rounded to float32 (out_f32).
+ * The base's matrix is the identity (or base[b]) as given, not computed. */
+#define MGS_POSE_MAXLINK 32
+typedef struct mgs_pose_tree {
+  int32_t nlink;
+  int32_t parent[MGS_POSE_MAXLINK];
+  double kin_tf[MGS_POSE_MAXLINK][7];
+  double joint_tf[MGS_POSE_MAXLINK][6];
+  double theta_scan[MGS_POSE_MAXLINK];
+} mgs_pose_tree;
+
+/* sizeof(mgs_pose_tree) as compiled (the Python mirror checks its layout) */
+int mgs_pose_tree_size(void);
+
+/* Host pointers, synchronous on `device`.  points npoint * 3, point_link
+ * npoint in [0, nlink], theta nbatch * nlink, base nbatch * 12 (row-major
+ * 3 x 4) or NULL, out_points nbatch * npoint * 3 (double, or float with
+ * out_f32 != 0), out_links nbatch * nlink * 7 or NULL: W_i(theta_b).  One
+ * workgroup poses points_per_group points of one joint state; 0 picks a size
+ * that fills the device at small nbatch.  kernel_ms (may be NULL): HIP events.
+ * MGS_EINVAL: nlink outside 1 .. MGS_POSE_MAXLINK, parent[i] outside
+ * -1 .. i - 1, a point_link outside 0 .. nlink, a negative count, more than
+ * 2^30 points or 65535 joint states, a null argument.  npoint == 0 or nbatch == 0: MGS_OK, nothing launched.  Theta is
+ * not checked: a non-finite joint value gives non-finite points. */
+int mgs_pose_cloud(int device, const mgs_pose_tree* tree, int npoint, const double* points,
+                   const int32_t* point_link, int nbatch, const double* theta, const double* base, int out_f32,
+                   void* out_points, double* out_links, int points_per_group, double* kernel_ms);
+
+/* The same on device pointers (tree stays a host pointer: it travels in the
+ * kernel arguments), asynchronous on `stream` of the current device: nothing
+ * is allocated, copied or waited for, so point_link is not read on the host:
+ * a point whose link lies outside 0 .. nlink comes out as NaN. */
+int mgs_pose_cloud_device(const mgs_pose_tree* tree, int npoint, const double* d_points, const int32_t* d_point_link,
+                          int nbatch, const double* d_theta, const double* d_base, int out_f32, void* d_out_points,
+                          double* d_out_links, int points_per_group, void* stream);
+
 /* Duration (ms) of the last rollout kernel launch, measured with HIP events
  * on the launch stream (waits for it). */
 double mgs_last_kernel_ms(mgs_batch* batch);

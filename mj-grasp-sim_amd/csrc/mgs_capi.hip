@@ -15,6 +15,7 @@
 #include "mgs_scan.hip"
 #include "mgs_contact.hip"
 #include "mgs_cloud.hip"
+#include "mgs_pose.hip"
 
 #include <cstdlib>
 
@@ -1569,6 +1570,93 @@ int mgs_scan_cloud(int device, const mgs_scan_scene* scene, int nview, const dou
     out_stats[4] = m;
     out_stats[5] = (int64_t)n;
   }
+  return MGS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// posed gripper cloud (csrc/mgs_pose.hip)
+}  // extern "C"
+namespace {
+// everything of a pose call the host can check without the arrays' contents
+int pose_check(const char* entry, const mgs_pose_tree* tree, int npoint, int nbatch, int ppg) {
+  if (!tree) return fail(MGS_EINVAL, "%s: null tree", entry);
+  if (tree->nlink < 1 || tree->nlink > MGS_POSE_MAXLINK) return fail(MGS_EINVAL, "%s: nlink must be 1 .. 32", entry);
+  for (int i = 0; i < tree->nlink; i++)
+    if (tree->parent[i] < -1 || tree->parent[i] >= i)
+      return fail(MGS_EINVAL, "%s: parent[i] must lie in -1 .. i - 1", entry);
+  if (npoint < 0 || nbatch < 0 || ppg < 0) return fail(MGS_EINVAL, "%s: negative size", entry);
+  if (npoint > (1 << 30)) return fail(MGS_EINVAL, "%s: more than 2^30 points", entry);
+  if (nbatch > 65535) return fail(MGS_EINVAL, "%s: at most 65535 joint states per call", entry);
+  return MGS_OK;
+}
+
+// points per workgroup: whole tiles, and with few joint states enough groups
+// for about four workgroups per CU of the device
+int pose_group_size(int npoint, int nbatch, int ppg) {
+  if (ppg > 0) return ppg;
+  const int want = (1024 + nbatch - 1) / nbatch;      // groups per joint state
+  int per = (npoint + want - 1) / want;
+  per = (per + MGS_POSE_THREADS - 1) / MGS_POSE_THREADS * MGS_POSE_THREADS;
+  return per < MGS_POSE_THREADS ? MGS_POSE_THREADS : per;
+}
+
+void pose_launch(const mgs_pose_tree* tree, int npoint, const double* dX, const int32_t* dL, int nbatch,
+                 const double* dTh, const double* dB, int out_f32, void* dO, double* dW, int ppg, hipStream_t st) {
+  const int per = pose_group_size(npoint, nbatch, ppg);
+  const dim3 grid((unsigned)((npoint + per - 1) / per), (unsigned)nbatch);
+  if (out_f32)
+    hipLaunchKernelGGL(mgs_pose_cloud_kernel<float>, grid, dim3(MGS_POSE_THREADS), 0, st, *tree, npoint, dX, dL, dTh,
+                       dB, (float*)dO, dW, per);
+  else
+    hipLaunchKernelGGL(mgs_pose_cloud_kernel<double>, grid, dim3(MGS_POSE_THREADS), 0, st, *tree, npoint, dX, dL, dTh,
+                       dB, (double*)dO, dW, per);
+}
+}  // namespace
+extern "C" {
+
+int mgs_pose_tree_size(void) { return (int)sizeof(mgs_pose_tree); }
+
+int mgs_pose_cloud(int device, const mgs_pose_tree* tree, int npoint, const double* points,
+                   const int32_t* point_link, int nbatch, const double* theta, const double* base, int out_f32,
+                   void* out_points, double* out_links, int points_per_group, double* kernel_ms) {
+  if (int rc = pose_check("mgs_pose_cloud", tree, npoint, nbatch, points_per_group)) return rc;
+  if (npoint > 0 && (!points || !point_link)) return fail(MGS_EINVAL, "mgs_pose_cloud: null argument%s");
+  for (int p = 0; p < npoint; p++)
+    if (point_link[p] < 0 || point_link[p] > tree->nlink)
+      return fail(MGS_EINVAL, "mgs_pose_cloud: a point_link lies outside 0 .. nlink%s");
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (npoint == 0 || nbatch == 0) return MGS_OK;
+  if (!theta || !out_points) return fail(MGS_EINVAL, "mgs_pose_cloud: null argument%s");
+  HIPCHK(hipSetDevice(device));
+  const size_t np = (size_t)npoint, nb = (size_t)nbatch, nl = (size_t)tree->nlink;
+  const size_t out_bytes = nb * np * 3 * (out_f32 ? sizeof(float) : sizeof(double));
+  DevBufs b;
+  double* dX = upload(b, points, 3 * np);
+  int32_t* dL = upload(b, point_link, np);
+  double* dTh = upload(b, theta, nb * nl);
+  double* dB = base ? upload(b, base, 12 * nb) : nullptr;
+  char* dO = b.get<char>(out_bytes);
+  double* dW = out_links ? b.get<double>(nb * nl * 7) : nullptr;
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
+  EvTimer t;
+  pose_launch(tree, npoint, dX, dL, nbatch, dTh, dB, out_f32, dO, dW, points_per_group, nullptr);
+  int rc = t.finish(kernel_ms);
+  if (rc != MGS_OK) return rc;
+  HIPCHK(hipMemcpy(out_points, dO, out_bytes, hipMemcpyDeviceToHost));
+  if (out_links) HIPCHK(hipMemcpy(out_links, dW, nb * nl * 7 * sizeof(double), hipMemcpyDeviceToHost));
+  return MGS_OK;
+}
+
+int mgs_pose_cloud_device(const mgs_pose_tree* tree, int npoint, const double* d_points, const int32_t* d_point_link,
+                          int nbatch, const double* d_theta, const double* d_base, int out_f32, void* d_out_points,
+                          double* d_out_links, int points_per_group, void* stream) {
+  if (int rc = pose_check("mgs_pose_cloud_device", tree, npoint, nbatch, points_per_group)) return rc;
+  if (npoint == 0 || nbatch == 0) return MGS_OK;
+  if (!d_points || !d_point_link || !d_theta || !d_out_points)
+    return fail(MGS_EINVAL, "mgs_pose_cloud_device: null argument%s");
+  pose_launch(tree, npoint, d_points, d_point_link, nbatch, d_theta, d_base, out_f32, d_out_points, d_out_links,
+              points_per_group, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
   return MGS_OK;
 }
 

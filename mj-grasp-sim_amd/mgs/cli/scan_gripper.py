@@ -27,8 +27,8 @@ from mgs.gripper.selector import get_gripper
 from mgs.obj.selector import generate_unique_hash
 
 
-def scan(cfg):
-    """the env after its scan, and what the scan returned"""
+def env_at_config(cfg):
+    """the scan env at the joint state the configuration names"""
     gripper = get_gripper(cfg.gripper)
     env = GripperScanEnv(gripper, device=cli_device())
     state = cfg.gripper.get("state")
@@ -39,6 +39,12 @@ def scan(cfg):
         if qpos is None or isinstance(qpos, str):       # absent, or an interpolation left unresolved
             qpos = cfg.gripper.qpos
         env.set_qpos(np.array(qpos, dtype=np.float64), env.get_joint_idxs(gripper.get_actuator_joint_names()))
+    return env
+
+
+def scan(cfg):
+    """the env after its scan, and what the scan returned"""
+    env = env_at_config(cfg)
     images, extrinsics, image_masks, segmentation = env.scan(
         num_images=int(cfg.num_images), width=int(cfg.get("width", 480)), height=int(cfg.get("height", 480)))
     return env, images, extrinsics, image_masks, segmentation

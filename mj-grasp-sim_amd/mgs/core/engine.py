@@ -95,6 +95,11 @@ def load_library(wide: bool = False):
     L.mgs_scan_cloud.argtypes = [ctypes.c_int, P(abi.ScanScene), ctypes.c_int, P(c_d), P(c_d), ctypes.c_int,
                                  ctypes.c_int, c_d, c_d, c_d, c_d, P(c_d), c_d, c_d, c_d, c_d, ctypes.c_int, P(c_d),
                                  P(c_f), ctypes.c_int, c_d, ctypes.c_int, P(c_f), P(c_f), P(c_i), P(c_i64), P(c_d)]
+    L.mgs_pose_tree_size.restype = ctypes.c_int
+    L.mgs_pose_cloud.argtypes = [ctypes.c_int, P(abi.PoseTree), ctypes.c_int, P(c_d), P(c_i), ctypes.c_int, P(c_d),
+                                 P(c_d), ctypes.c_int, vp, P(c_d), ctypes.c_int, P(c_d)]
+    L.mgs_pose_cloud_device.argtypes = [P(abi.PoseTree), ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp,
+                                        vp, ctypes.c_int, vp]
     L.mgs_supports_nv.argtypes = [ctypes.c_int]
     L.mgs_supports_nv.restype = ctypes.c_int
     L.mgs_rollout_grid.argtypes = [vp, ctypes.c_int]
@@ -761,6 +766,102 @@ def contact_optimize(kin_desc, rot_init, pos_init, targets, normals, device=0):
                                   ptr(oR, d), ptr(oP, d), ptr(oJ, d), ptr(oL, d), ctypes.byref(ms)),
            "mgs_contact_optimize", L)
     return dict(rot=oR, pos=oP, joints=oJ, loss=oL, kernel_ms=ms.value)
+
+
+def _pose_tree(tree):
+    return tree if isinstance(tree, abi.PoseTree) else abi.make_pose_tree(tree)
+
+
+def _pose_base(base, nb):
+    """grasp poses (B, 4, 4) or (B, 3, 4) as the rows the kernel reads: (B, 12)"""
+    if base is None:
+        return None
+    g = np.asarray(base, np.float64)
+    if g.shape not in ((nb, 4, 4), (nb, 3, 4)):
+        raise ValueError(f"base is (B, 4, 4) or (B, 3, 4) with B = {nb}, not {g.shape}")
+    return np.ascontiguousarray(g[:, :3, :]).reshape(nb, 12)
+
+
+def pose_cloud(tree, points, point_link, theta, base=None, dtype=np.float32, points_per_group=0, device=0):
+    """the cloud of a scanned gripper at B joint states (mgs_pose_cloud).
+    tree: a mgs.sampler.kin.tree.KinematicTree (or an abi.PoseTree); points
+    (P, 3) as scanned at tree.theta_scan; point_link (P,) in [0, nlink] (0 = the
+    base, k = link k - 1); theta (B, nlink); base: B grasp poses (B, 4, 4) that
+    place the posed cloud, or None; dtype float32 or float64 (the arithmetic is
+    f64, only the store is rounded).  Returns dict(points (B, P, 3), links
+    (B, nlink, 7): W_i(theta_b) as wxyz + xyz, kernel_ms)."""
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("dtype is float32 or float64")
+    T = _pose_tree(tree)
+    nl = int(T.nlink)
+    x = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    link = np.ascontiguousarray(point_link, np.int32).reshape(-1)
+    th = np.ascontiguousarray(theta, np.float64)
+    if th.ndim != 2 or th.shape[1] != nl:
+        raise ValueError(f"theta is (B, nlink = {nl}), not {th.shape}")
+    if len(link) != len(x):
+        raise ValueError(f"{len(x)} points, {len(link)} point links")
+    nb = len(th)
+    g = _pose_base(base, nb)
+    L = _device_lib(device)
+    out = np.zeros((nb, len(x), 3), dt)
+    links = np.zeros((nb, nl, 7))
+    ms = ctypes.c_double(0.0)
+    d = ctypes.c_double
+    _check(L.mgs_pose_cloud(device, ctypes.byref(T), len(x), ptr(x, d), ptr(link, ctypes.c_int32), nb, ptr(th, d),
+                            None if g is None else ptr(g, d), int(dt == np.dtype(np.float32)),
+                            out.ctypes.data_as(ctypes.c_void_p), ptr(links, d), int(points_per_group),
+                            ctypes.byref(ms)), "mgs_pose_cloud", L)
+    return dict(points=out, links=links, kernel_ms=ms.value)
+
+
+def pose_cloud_torch(tree, points, point_link, theta, base=None, dtype=None, points_per_group=0, out=None):
+    """pose_cloud on torch tensors of one GPU (mgs_pose_cloud_device): points
+    (P, 3) float64, point_link (P,) int32, theta (B, nlink) float64 and base
+    (B, 3, 4) or (B, 4, 4) float64 or None, all on the same device.  The launch
+    goes to torch's current stream of that device; nothing is copied to the
+    host.  Returns dict(points (B, P, 3) of `dtype` (default float32), links
+    (B, nlink, 7) float64), tensors on the device.  A point_link outside
+    [0, nlink] is not refused here: its point comes out as NaN."""
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError("dtype is torch.float32 or torch.float64")
+    T = _pose_tree(tree)
+    nl = int(T.nlink)
+    dev = points.device
+    if dev.type != "cuda":
+        raise EngineError("pose_cloud_torch: the tensors must be on a GPU (the host entry is pose_cloud)")
+    x = points.to(torch.float64).contiguous().reshape(-1, 3)
+    link = point_link.to(torch.int32).contiguous().reshape(-1)
+    th = theta.to(torch.float64).contiguous()
+    if th.ndim != 2 or th.shape[1] != nl:
+        raise ValueError(f"theta is (B, nlink = {nl}), not {tuple(th.shape)}")
+    if len(link) != len(x):
+        raise ValueError(f"{len(x)} points, {len(link)} point links")
+    nb = len(th)
+    g = None
+    if base is not None:
+        if tuple(base.shape) not in ((nb, 4, 4), (nb, 3, 4)):
+            raise ValueError(f"base is (B, 4, 4) or (B, 3, 4) with B = {nb}, not {tuple(base.shape)}")
+        g = base.to(torch.float64)[:, :3, :].contiguous()
+    for name, a in (("point_link", link), ("theta", th), ("base", g)):
+        if a is not None and a.device != dev:
+            raise ValueError(f"pose_cloud_torch: {name} is on {a.device}, points on {dev}")
+    L = _device_lib(dev.index or 0)
+    if out is None:
+        out = torch.empty((nb, len(x), 3), dtype=dtype, device=dev)
+    elif out.dtype != dtype or tuple(out.shape) != (nb, len(x), 3) or not out.is_contiguous() or out.device != dev:
+        raise ValueError("pose_cloud_torch: out must be a contiguous (B, P, 3) tensor of dtype on the points' device")
+    links = torch.empty((nb, nl, 7), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(L.mgs_pose_cloud_device(ctypes.byref(T), len(x), x.data_ptr(), link.data_ptr(), nb, th.data_ptr(),
+                                       None if g is None else g.data_ptr(), int(dtype == torch.float32),
+                                       out.data_ptr(), links.data_ptr(), int(points_per_group), stream or None),
+               "mgs_pose_cloud_device", L)
+    return dict(points=out, links=links)
 
 
 def tree_probe(a, c, n):

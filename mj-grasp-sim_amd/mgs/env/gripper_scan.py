@@ -237,3 +237,29 @@ class GripperScanEnv:
         _, geoms = self._segment_geoms(spec)
         member = np.stack([np.isin(geom, g) for g in geoms]) if geoms else np.zeros((0, len(geom)), bool)
         return points, geom, member
+
+    # -- posing ---------------------------------------------------------------------
+    def kinematic_tree(self):
+        """the model's hinge and slide joints as a mgs.sampler.kin.tree
+        KinematicTree at the current free-joint pose; theta_scan is the current
+        joint state (what a scan taken now shows)"""
+        from mgs.sampler.kin.tree import tree_from_model
+        return tree_from_model(self.model, self.qpos)
+
+    def pose_cloud(self, points, point_geom, joints, poses=None, dtype=np.float32, points_per_group=0):
+        """the cloud of cloud() -- scanned at the current joint state -- at B
+        joint states on the GPU (mgs_pose_cloud).  joints (B, nlink): theta =
+        qpos - qpos0 per link of kinematic_tree() (tree.theta_from_qpos /
+        theta_from_named build it); poses (B, 4, 4): grasp poses in the contact
+        frame, which is the scan's world frame (set_pose at identity @
+        base_to_contact_transform()), so the scene-frame cloud is pose_b . p.
+        Returns dict(points (B, P, 3) of dtype, links, kernel_ms, point_link)."""
+        from mgs.core.engine import pose_cloud
+        tree = self.kinematic_tree()
+        geom = np.asarray(point_geom, np.int64).reshape(-1)
+        if len(geom) and (geom.min() < 0 or geom.max() >= len(self.model.geom_bodyid)):
+            raise ValueError("point_geom holds an index that is no geom of the model")
+        link = tree.link_of_geoms(self.model)[geom]
+        res = pose_cloud(tree, points, link, joints, base=poses, dtype=dtype, points_per_group=points_per_group,
+                         device=self.device)
+        return dict(res, point_link=link)

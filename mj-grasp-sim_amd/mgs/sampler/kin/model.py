@@ -13,6 +13,13 @@ csrc/mgs_contact.hip (device) and oracle/mgs_contact_oracle.c (checker).
 Only the Shadow Hand is provided: it is the dexterous hand whose simulation
 (mgs.gripper.shadow) this build evaluates; the LEAP hand has no gripper model
 here, so its kinematic table is not carried.
+
+Posing a scanned cloud by joint values (the reference's
+kinematic_pcd_transform, base.py:34-77) does not need a hand-kept table:
+mgs.sampler.kin.tree turns this table (tree_from_kinematics) or the compiled
+MJCF model of any gripper (tree_from_model) into a KinematicTree, which
+csrc/mgs_pose.hip consumes.  get_kinematics stays the contact sampler's lookup
+and keeps raising for every gripper but the Shadow Hand.
 """
 from dataclasses import dataclass, field
 
