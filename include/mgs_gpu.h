@@ -808,6 +808,56 @@ int mgs_scan_cloud(int device, const mgs_scan_scene* scene, int nview, const dou
                    const float* colors, int ncolor, double voxel_size, int num_points, float* out_points,
                    float* out_colors, int32_t* out_n, int64_t* out_stats, double* stage_ms);
 
+/* Many clouds, one pick launch (mgs_cloud_fps_batch_kernel: one workgroup per
+ * cloud, none waiting on another).  ncloud clouds, cloud c = points[3 off[c] ..
+ * 3 off[c + 1]) (off: ncloud + 1, ascending, off[0] = 0), k[c] picks each into
+ * out_idx[koff[c] ..), koff the running sum of k.  Per cloud exactly the
+ * indices and out_nevals[c] (may be NULL) that mgs_scan_fps(points_c, n_c, k[c],
+ * bucket_size) returns; a cloud with k[c] = 0 (an empty one included) takes no
+ * part and reports 0 evaluations.  kernel_ms (may be NULL): set-up and pick.
+ * Every cloud is checked by the rules of mgs_scan_fps before anything is
+ * launched or written; the error text names the cloud.  ncloud = 0: MGS_OK. */
+int mgs_scan_fps_batch(int device, int ncloud, const double* points, const int64_t* off, const int32_t* k,
+                       double bucket_size, int32_t* out_idx, int64_t* out_nevals, double* kernel_ms);
+
+/* The order in which the batched pick's workgroups take their jobs: heaviest
+ * first, by descending n[c] * k[c], equal work by ascending c (workgroups are
+ * dispatched in block order; no result depends on it).  order: ncloud.  Host
+ * only. */
+int mgs_scan_fps_order(int ncloud, const int64_t* n, const int32_t* k, int32_t* order);
+
+/* One scene of mgs_scan_cloud_batch: what mgs_scan_cloud takes and returns per
+ * scene.  out_points / out_colors: num_points * 3 float32, out_n rows written;
+ * out_stats as mgs_scan_cloud's; stage_ms: render, points + compaction, voxels
+ * (the pick is the batch's). */
+typedef struct mgs_scan_cloud_job {
+  const mgs_scan_scene *scene;
+  const float *colors;       /* ncolor * 3 */
+  float *out_points;
+  float *out_colors;
+  int64_t out_stats[8];
+  double stage_ms[3];
+  int32_t ncolor, num_points;
+  int32_t out_n, reserved;
+} mgs_scan_cloud_job;
+int mgs_scan_cloud_job_size(void);
+
+/* njob scenes seen by the same cameras with the same parameters: per job the
+ * result of mgs_scan_cloud.  Render, points, compaction and voxels run scene
+ * after scene in job order, each scene's scratch released (the voxel stage's)
+ * or reused (the images) before the next; only a scene's voxels and its pick
+ * set-up live until the one batched pick of all jobs with at least num_points
+ * voxels (and num_points > 0); the others return every voxel in voxel order.
+ * pick_ms (may be NULL): that launch.  Every argument of every job is checked
+ * before anything is launched or written (MGS_EINVAL, the text names the job);
+ * an error only the device finds (MGS_ECAPACITY, MGS_ENOMEM, MGS_EHIP) names
+ * its job too, and then no job's outputs are written: they are copied out
+ * after every job has succeeded.  njob = 0: MGS_OK. */
+int mgs_scan_cloud_batch(int device, int njob, mgs_scan_cloud_job* jobs, int nview, const double* cam_pos,
+                         const double* cam_rot, int width, int height, double fx, double fy, double cx, double cy,
+                         const double* extrinsics, double pfx, double pfy, double pcx, double pcy, int erode_iters,
+                         const double* region, double voxel_size, double* pick_ms);
+
 /* ---------------------------------------------------------------------------
  * Posed gripper cloud (csrc/mgs_pose.hip): the cloud of a scanned gripper at
  * each of nbatch joint states -- what the reference's kinematic_pcd_transform

@@ -2,6 +2,7 @@
 // include/mgs_gpu.h (model upload, batch buffers, kernel launches, timing).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -1259,9 +1260,11 @@ int cloud_bounds(DevBufs& b, const double* dX, const uint8_t* dK, size_t n, clou
 // counted grid (ncell) and the points' cells (npts) -> *start (occupied + 1:
 // first slot of every occupied cell in ascending cell, then npts), *slot_idx
 // (npts: point per slot, unordered inside a cell), *nocc.  cap >= 0: more
-// occupied cells than cap is MGS_ECAPACITY with *nocc set.
-int cloud_slots(DevBufs& b, uint32_t* grid, size_t ncell, const uint32_t* pcell, uint32_t npts, int64_t cap,
-                uint32_t** start, uint32_t** slot_idx, uint32_t* nocc) {
+// occupied cells than cap is MGS_ECAPACITY with *nocc set.  *start and
+// *slot_idx come from `keep`, what only this step needs from `b` (the two may
+// be one; a batch keeps the first and releases the second scene by scene).
+int cloud_slots(DevBufs& b, DevBufs& keep, uint32_t* grid, size_t ncell, const uint32_t* pcell, uint32_t npts,
+                int64_t cap, uint32_t** start, uint32_t** slot_idx, uint32_t* nocc) {
   const size_t nb = cloud_blocks(ncell);
   cloud_u64* sums = b.get<cloud_u64>(nb);
   CloudHdr* dH = b.get<CloudHdr>(1);
@@ -1275,9 +1278,9 @@ int cloud_slots(DevBufs& b, uint32_t* grid, size_t ncell, const uint32_t* pcell,
   *nocc = (uint32_t)(h.total >> 32);
   if ((uint32_t)h.total != npts || *nocc > npts) return fail(MGS_EHIP, "cloud grid: the cell counts do not add up%s");
   if (cap >= 0 && (int64_t)*nocc > cap) return MGS_ECAPACITY;
-  *start = b.get<uint32_t>((size_t)*nocc + 1);
-  *slot_idx = b.get<uint32_t>(npts);
-  if (!b.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
+  *start = keep.get<uint32_t>((size_t)*nocc + 1);
+  *slot_idx = keep.get<uint32_t>(npts);
+  if (!keep.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
   hipLaunchKernelGGL(cloud_cell_offsets_kernel, dim3((unsigned)nb), dim3(MGS_CLOUD_BLOCK), 0, nullptr, grid, ncell, sums,
                      *start, *nocc, npts);
   hipLaunchKernelGGL(cloud_scatter_kernel, dim3((npts + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK), dim3(MGS_CLOUD_BLOCK),
@@ -1288,8 +1291,9 @@ int cloud_slots(DevBufs& b, uint32_t* grid, size_t ncell, const uint32_t* pcell,
 
 // the voxel stage on device arrays: dX (n * 3), dK (n or NULL), features dF
 // (n * nfeat) or, with dSeg, the rows dCol[dSeg] (nfeat 3).  `mid` (or NULL)
-// is recorded behind the compaction.  cap as cloud_slots.
-int cloud_voxels_dev(DevBufs& b, const double* dX, const uint8_t* dK, size_t n, const float* dF, int nfeat,
+// is recorded behind the compaction.  cap as cloud_slots.  The voxels V leaves
+// come from `keep`, everything else from `b` (as cloud_slots).
+int cloud_voxels_dev(DevBufs& b, DevBufs& keep, const double* dX, const uint8_t* dK, size_t n, const float* dF, int nfeat,
                      const int32_t* dSeg, const float* dCol, int ncolor, double voxel_size, int64_t cap, CloudVox* V,
                      hipEvent_t mid) {
   *V = CloudVox();
@@ -1330,20 +1334,23 @@ int cloud_voxels_dev(DevBufs& b, const double* dX, const uint8_t* dK, size_t n, 
                      sums, dF, nfeat, dSeg, dCol, ncolor, G, cpts, cfeat, pcell, grid);
   if (mid) hipEventRecord(mid, nullptr);
   uint32_t *start = nullptr, *slot_idx = nullptr;
-  rc = cloud_slots(b, grid, (size_t)ncell, pcell, m, cap, &start, &slot_idx, &V->nvox);
+  rc = cloud_slots(b, b, grid, (size_t)ncell, pcell, m, cap, &start, &slot_idx, &V->nvox);
   if (rc != MGS_OK) return rc == MGS_ECAPACITY ? fail(rc, "cloud voxels: more voxels than the outputs hold%s") : rc;
-  V->vpts = b.get<double>(3 * (size_t)V->nvox);
-  V->vfeat = b.get<float>((size_t)nfeat * V->nvox);
-  V->vcnt = b.get<int32_t>(V->nvox);
-  if (!b.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
+  V->vpts = keep.get<double>(3 * (size_t)V->nvox);
+  V->vfeat = keep.get<float>((size_t)nfeat * V->nvox);
+  V->vcnt = keep.get<int32_t>(V->nvox);
+  if (!keep.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
   hipLaunchKernelGGL(cloud_voxel_kernel, dim3((V->nvox + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK), dim3(MGS_CLOUD_BLOCK),
                      0, nullptr, start, V->nvox, slot_idx, cpts, cfeat, nfeat, V->vpts, V->vfeat, V->vcnt);
   HIPCHK(hipGetLastError());
   return MGS_OK;
 }
 
-// the pick on device arrays: dX (n * 3, finite), 1 <= k <= n; dOut (k), dEv (1)
-int cloud_fps_dev(DevBufs& b, const double* dX, int n, int k, double bucket_size, int32_t* dOut, cloud_u64* dEv) {
+// the pick's set-up on device arrays: dX (n * 3, finite), 1 <= k <= n; dOut (k),
+// dEv (1).  *J = the arguments of the pick; the arrays they name come from
+// `keep` and live until the pick has run, the set-up's own from `b`.
+int cloud_fps_setup(DevBufs& b, DevBufs& keep, const double* dX, int n, int k, double bucket_size, int32_t* dOut,
+                    cloud_u64* dEv, CloudFpsJob* J) {
   cloud_u64* sums = nullptr;
   CloudHdr h;
   int rc = cloud_bounds(b, dX, nullptr, (size_t)n, &sums, &h);
@@ -1371,31 +1378,182 @@ int cloud_fps_dev(DevBufs& b, const double* dX, int n, int k, double bucket_size
   const unsigned pb = ((unsigned)n + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK;
   hipLaunchKernelGGL(cloud_fps_cell_kernel, dim3(pb), dim3(MGS_CLOUD_BLOCK), 0, nullptr, dX, (uint32_t)n, G, pcell, grid);
   uint32_t *start = nullptr, *slot_idx = nullptr, nbkt = 0;
-  rc = cloud_slots(b, grid, ncell, pcell, (uint32_t)n, -1, &start, &slot_idx, &nbkt);
+  rc = cloud_slots(b, keep, grid, ncell, pcell, (uint32_t)n, -1, &start, &slot_idx, &nbkt);
   if (rc != MGS_OK) return rc;
-  double* bx = b.get<double>(3 * (size_t)n);
-  double* bdist = b.get<double>((size_t)n);
-  double* bbox = b.get<double>(6 * (size_t)nbkt);
-  double* bmax = b.get<double>(nbkt);
-  int32_t* bidx = b.get<int32_t>(nbkt);
-  if (!b.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
+  double* bx = keep.get<double>(3 * (size_t)n);
+  double* bdist = keep.get<double>((size_t)n);
+  double* bbox = keep.get<double>(6 * (size_t)nbkt);
+  double* bmax = keep.get<double>(nbkt);
+  int32_t* bidx = keep.get<int32_t>(nbkt);
+  if (!keep.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
   hipLaunchKernelGGL(cloud_fps_gather_kernel, dim3(pb), dim3(MGS_CLOUD_BLOCK), 0, nullptr, dX, (uint32_t)n, slot_idx, bx,
                      bdist);
   hipLaunchKernelGGL(cloud_fps_box_kernel, dim3((nbkt + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK), dim3(MGS_CLOUD_BLOCK), 0,
                      nullptr, start, nbkt, slot_idx, bx, bbox, bmax, bidx);
-  hipLaunchKernelGGL(mgs_cloud_fps_kernel, dim3(1), dim3(MGS_CLOUD_FPS_THREADS), 0, nullptr, dX, bx, slot_idx, bdist,
-                     start, bbox, bmax, bidx, (int)nbkt, k, dOut, dEv);
+  HIPCHK(hipGetLastError());
+  *J = CloudFpsJob{dX, bx, slot_idx, bdist, start, bbox, bmax, bidx, dOut, dEv, (int32_t)nbkt, (int32_t)k};
+  return MGS_OK;
+}
+
+// one cloud's pick: its set-up and the single-cloud kernel
+int cloud_fps_dev(DevBufs& b, const double* dX, int n, int k, double bucket_size, int32_t* dOut, cloud_u64* dEv) {
+  CloudFpsJob J;
+  int rc = cloud_fps_setup(b, b, dX, n, k, bucket_size, dOut, dEv, &J);
+  if (rc != MGS_OK) return rc;
+  hipLaunchKernelGGL(mgs_cloud_fps_kernel, dim3(1), dim3(MGS_CLOUD_FPS_THREADS), 0, nullptr, J.x, J.bx, J.borig, J.bdist,
+                     J.start, J.bbox, J.bmax, J.bidx, (int)J.nb, (int)J.k, J.out, J.nevals);
   HIPCHK(hipGetLastError());
   return MGS_OK;
 }
 
+// heaviest first: descending n * k, equal work by ascending index
+void cloud_fps_order(int ncloud, const int64_t* n, const int32_t* k, int32_t* order) {
+  for (int c = 0; c < ncloud; c++) order[c] = c;
+  std::stable_sort(order, order + ncloud, [&](int32_t a, int32_t b) { return n[a] * (int64_t)k[a] > n[b] * (int64_t)k[b]; });
+}
+
+// the picks of jobs (n[j] = the points of job j) in one launch, heaviest first; *ms (or NULL) = its time
+int cloud_fps_launch_batch(DevBufs& b, const std::vector<CloudFpsJob>& jobs, const std::vector<int64_t>& n, double* ms) {
+  if (ms) *ms = 0.0;
+  const int nj = (int)jobs.size();
+  if (nj == 0) return MGS_OK;
+  std::vector<int32_t> k(nj), order(nj);
+  for (int j = 0; j < nj; j++) k[j] = jobs[j].k;
+  cloud_fps_order(nj, n.data(), k.data(), order.data());
+  std::vector<CloudFpsJob> table(nj);
+  for (int j = 0; j < nj; j++) table[j] = jobs[order[j]];
+  CloudFpsJob* dJ = upload(b, table.data(), (size_t)nj);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
+  EvTimer t;
+  hipLaunchKernelGGL(mgs_cloud_fps_batch_kernel, dim3((unsigned)nj), dim3(MGS_CLOUD_FPS_THREADS), 0, nullptr, dJ);
+  return t.finish(ms);
+}
+
+// the current error text behind "<entry>: <what> <index>: "
+int fail_at(int rc, const char* entry, const char* what, int index) {
+  const std::string inner = g_err;
+  char head[128];
+  snprintf(head, sizeof(head), "%s: %s %d: ", entry, what, index);
+  g_err = head + inner;
+  return rc;
+}
+
 bool cloud_size_ok(double v) { return v > 0.0 && is_finite(v); }
+
+// the argument rules of mgs_scan_fps (one cloud of mgs_scan_fps_batch)
+int scan_fps_check(const double* points, int64_t n, int64_t k, double bucket_size, const int32_t* out_idx) {
+  if (n < 0 || k < 0 || (k > 0 && n == 0) || k > n) return fail(MGS_EINVAL, "mgs_scan_fps: need 0 <= k <= n%s");
+  if (n > 0x7fffffff) return fail(MGS_EINVAL, "mgs_scan_fps: more than 2^31 - 1 points%s");
+  if (!cloud_size_ok(bucket_size)) return fail(MGS_EINVAL, "mgs_scan_fps: bucket_size must be positive and finite%s");
+  if (k > 0 && (!points || !out_idx)) return fail(MGS_EINVAL, "mgs_scan_fps: null argument%s");
+  if (k > 0)
+    for (size_t j = 0; j < 3 * (size_t)n; j++)
+      if (!is_finite(points[j])) return fail(MGS_EINVAL, "mgs_scan_fps: a point is not finite%s");
+  return MGS_OK;
+}
+
+// the argument rules of mgs_scan_cloud: what every scene of a batch shares ...
+int scan_cloud_check_views(const char* entry, int nview, const double* cam_pos, const double* cam_rot, int width,
+                           int height, double fx, double fy, const double* extrinsics, double pfx, double pfy,
+                           int erode_iters, double voxel_size, size_t* npix) {
+  if (int rc = check_views(entry, nview, width, height, fx, fy, true, npix)) return rc;
+  if (!(pfx > 0.0) || !(pfy > 0.0)) return fail(MGS_EINVAL, "%s: focal lengths must be positive", entry);
+  if (erode_iters < 0 || erode_iters > 64) return fail(MGS_EINVAL, "%s: erode_iters must be 0 .. 64", entry);
+  if (!cloud_size_ok(voxel_size)) return fail(MGS_EINVAL, "%s: voxel_size must be positive and finite", entry);
+  if (*npix > 0 && (!cam_pos || !cam_rot || !extrinsics)) return fail(MGS_EINVAL, "%s: null argument", entry);
+  return MGS_OK;
+}
+// ... and one scene's own
+int scan_cloud_check_scene(const mgs_scan_scene* scene, const float* colors, int ncolor, int num_points,
+                           const float* out_points, const float* out_colors) {
+  if (!scene) return fail(MGS_EINVAL, "mgs_scan_cloud: null scene%s");
+  if (num_points < 0 || ncolor < 0) return fail(MGS_EINVAL, "mgs_scan_cloud: negative size%s");
+  const char* bad = scan_scene_error(scene);
+  if (bad[0]) return fail(MGS_EINVAL, "mgs_scan_cloud: scene: %s", bad);
+  for (int d = 0; d < scene->ndraw; d++)
+    if (scene->draw_id[d] < 0 || scene->draw_id[d] >= ncolor)
+      return fail(MGS_EINVAL, "mgs_scan_cloud: a draw_id has no row of colors%s");
+  if ((ncolor > 0 && !colors) || (num_points > 0 && (!out_points || !out_colors)))
+    return fail(MGS_EINVAL, "mgs_scan_cloud: null argument%s");
+  return MGS_OK;
+}
 
 struct CloudEvents {
   hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   CloudEvents() { for (auto& x : e) hipEventCreate(&x); }
   ~CloudEvents() { for (auto& x : e) hipEventDestroy(x); }
 };
+
+// what mgs_scan_cloud_batch shares between its scenes, on the device: the
+// cameras and the images (every scene renders into the same ones)
+struct CloudBatchViews {
+  size_t n = 0;
+  int nview = 0, width = 0, height = 0, erode_iters = 0;
+  double fx = 0, fy = 0, cx = 0, cy = 0, pfx = 0, pfy = 0, pcx = 0, pcy = 0, voxel_size = 0;
+  const double* rg = nullptr;
+  double *dCP = nullptr, *dCR = nullptr, *dE = nullptr, *dD = nullptr, *dD32 = nullptr, *dP = nullptr;
+  int32_t *dS = nullptr, *dT = nullptr, *dN = nullptr;
+  uint8_t* dK = nullptr;
+};
+// what one scene of a batch leaves on the device until the batched pick
+struct CloudBatchScene {
+  CloudVox V;
+  int m = 0;                      // rows it returns
+  float *oP = nullptr, *oC = nullptr;
+  int32_t* dIdx = nullptr;        // the pick's indices (NULL: every voxel in voxel order)
+  double ms[3] = {0.0, 0.0, 0.0};
+};
+// render, points, compaction and voxels of one scene, and its pick's set-up
+// (*picked, *J).  The scene's own arrays (its drawables, the compacted points,
+// the dense grid, the set-up's grid) live in a DevBufs of this call, released
+// on return; what the pick and the output need comes from `keep`.
+int cloud_batch_scene(DevBufs& keep, const CloudBatchViews& v, const mgs_scan_cloud_job& job, cloud_u64* dEv,
+                      CloudBatchScene* out, bool* picked, CloudFpsJob* J) {
+  DevBufs s;
+  ScanDev S = scan_upload_scene(s, job.scene);
+  float* dCol = upload(s, job.colors, 3 * (size_t)job.ncolor);
+  if (!s.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
+  CloudEvents ev;
+  hipEventRecord(ev.e[0], nullptr);
+  launch_scan_render(S, v.dCP, v.dCR, v.nview, v.width, v.height, v.fx, v.fy, v.cx, v.cy, v.dD, v.dS, v.dT, v.dN);
+  hipEventRecord(ev.e[1], nullptr);
+  hipLaunchKernelGGL(cloud_round_f32_kernel, dim3((unsigned)((v.n + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK)),
+                     dim3(MGS_CLOUD_BLOCK), 0, nullptr, v.dD, v.n, v.dD32);
+  hipLaunchKernelGGL(mgs_scan_points_kernel, dim3((unsigned)((v.n + 255) / 256)), dim3(256), 0, nullptr, v.nview, v.width,
+                     v.height, v.dD32, v.dS, v.dE, v.pfx, v.pfy, v.pcx, v.pcy, v.erode_iters, v.rg[0], v.rg[1], v.rg[2],
+                     v.rg[3], v.rg[4], v.rg[5], v.dP, v.dK);
+  HIPCHK(hipGetLastError());
+  int rc = cloud_voxels_dev(s, keep, v.dP, v.dK, v.n, nullptr, 3, v.dS, dCol, job.ncolor, v.voxel_size, -1, &out->V,
+                            ev.e[2]);
+  if (rc != MGS_OK) return rc;
+  hipEventRecord(ev.e[3], nullptr);
+  const int nvox = (int)out->V.nvox;
+  out->m = nvox >= job.num_points ? job.num_points : nvox;
+  *picked = false;
+  if (out->m > 0) {
+    out->oP = keep.get<float>(3 * (size_t)out->m);
+    out->oC = keep.get<float>(3 * (size_t)out->m);
+    if (nvox >= job.num_points) {
+      double* dX = keep.get<double>(3 * (size_t)nvox);
+      out->dIdx = keep.get<int32_t>((size_t)out->m);
+      if (!keep.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
+      hipLaunchKernelGGL(cloud_round_f32_kernel, dim3((3 * (unsigned)nvox + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK),
+                         dim3(MGS_CLOUD_BLOCK), 0, nullptr, out->V.vpts, 3 * (size_t)nvox, dX);
+      rc = cloud_fps_setup(s, keep, dX, nvox, out->m, 8.0 * v.voxel_size, out->dIdx, dEv, J);
+      if (rc != MGS_OK) return rc;
+      *picked = true;
+    }
+    if (!keep.ok) return fail(MGS_ENOMEM, "device allocation failed%s");
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());      // the scene's own arrays go when this returns
+  for (int i = 0; i < 3; i++) {
+    float f = 0.f;
+    hipEventElapsedTime(&f, ev.e[i], ev.e[i + 1]);
+    out->ms[i] = f;
+  }
+  return MGS_OK;
+}
 }  // namespace
 extern "C" {
 
@@ -1423,7 +1581,7 @@ int mgs_scan_voxels(int device, int n, const double* points, const uint8_t* keep
   if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
   EvTimer t;
   CloudVox V;
-  int rc = cloud_voxels_dev(b, dX, dK, nn, dF, nfeat, nullptr, nullptr, 0, voxel_size, cap, &V, nullptr);
+  int rc = cloud_voxels_dev(b, b, dX, dK, nn, dF, nfeat, nullptr, nullptr, 0, voxel_size, cap, &V, nullptr);
   if (rc == MGS_ECAPACITY) { *out_nvox = (int32_t)V.nvox; return rc; }      // 0xffffffff = -1: the grid itself
   if (rc != MGS_OK) return rc;
   rc = t.finish(kernel_ms);
@@ -1440,12 +1598,7 @@ int mgs_scan_voxels(int device, int n, const double* points, const uint8_t* keep
 
 int mgs_scan_fps(int device, const double* points, int n, int k, double bucket_size, int32_t* out_idx,
                  int64_t* out_nevals, double* kernel_ms) {
-  if (n < 0 || k < 0 || (k > 0 && n == 0) || k > n) return fail(MGS_EINVAL, "mgs_scan_fps: need 0 <= k <= n%s");
-  if (!cloud_size_ok(bucket_size)) return fail(MGS_EINVAL, "mgs_scan_fps: bucket_size must be positive and finite%s");
-  if (k > 0 && (!points || !out_idx)) return fail(MGS_EINVAL, "mgs_scan_fps: null argument%s");
-  if (k > 0)
-    for (size_t j = 0; j < 3 * (size_t)n; j++)
-      if (!is_finite(points[j])) return fail(MGS_EINVAL, "mgs_scan_fps: a point is not finite%s");
+  if (int rc = scan_fps_check(points, n, k, bucket_size, out_idx)) return rc;
   if (k == 0) {
     if (out_nevals) *out_nevals = 0;
     return MGS_OK;
@@ -1475,19 +1628,11 @@ int mgs_scan_cloud(int device, const mgs_scan_scene* scene, int nview, const dou
                    float* out_colors, int32_t* out_n, int64_t* out_stats, double* stage_ms) {
   if (!scene) return fail(MGS_EINVAL, "mgs_scan_cloud: null scene%s");
   size_t n = 0;
-  if (int rc = check_views("mgs_scan_cloud", nview, width, height, fx, fy, true, &n)) return rc;
-  if (num_points < 0 || ncolor < 0) return fail(MGS_EINVAL, "mgs_scan_cloud: negative size%s");
-  if (!(pfx > 0.0) || !(pfy > 0.0)) return fail(MGS_EINVAL, "mgs_scan_cloud: focal lengths must be positive%s");
-  if (erode_iters < 0 || erode_iters > 64) return fail(MGS_EINVAL, "mgs_scan_cloud: erode_iters must be 0 .. 64%s");
-  if (!cloud_size_ok(voxel_size)) return fail(MGS_EINVAL, "mgs_scan_cloud: voxel_size must be positive and finite%s");
-  const char* bad = scan_scene_error(scene);
-  if (bad[0]) return fail(MGS_EINVAL, "mgs_scan_cloud: scene: %s", bad);
-  for (int d = 0; d < scene->ndraw; d++)
-    if (scene->draw_id[d] < 0 || scene->draw_id[d] >= ncolor)
-      return fail(MGS_EINVAL, "mgs_scan_cloud: a draw_id has no row of colors%s");
-  if (!out_n || (ncolor > 0 && !colors) || (num_points > 0 && (!out_points || !out_colors)) ||
-      (n > 0 && (!cam_pos || !cam_rot || !extrinsics)))
-    return fail(MGS_EINVAL, "mgs_scan_cloud: null argument%s");
+  if (int rc = scan_cloud_check_views("mgs_scan_cloud", nview, cam_pos, cam_rot, width, height, fx, fy, extrinsics, pfx,
+                                      pfy, erode_iters, voxel_size, &n))
+    return rc;
+  if (int rc = scan_cloud_check_scene(scene, colors, ncolor, num_points, out_points, out_colors)) return rc;
+  if (!out_n) return fail(MGS_EINVAL, "mgs_scan_cloud: null argument%s");
   if (out_stats) for (int i = 0; i < 8; i++) out_stats[i] = 0;
   if (stage_ms) for (int i = 0; i < 4; i++) stage_ms[i] = 0.0;
   if (n == 0) { *out_n = 0; return MGS_OK; }
@@ -1518,7 +1663,7 @@ int mgs_scan_cloud(int device, const mgs_scan_scene* scene, int nview, const dou
                      dK);
   HIPCHK(hipGetLastError());
   CloudVox V;
-  int rc = cloud_voxels_dev(b, dP, dK, n, nullptr, 3, dS, dCol, ncolor, voxel_size, -1, &V, ev.e[2]);
+  int rc = cloud_voxels_dev(b, b, dP, dK, n, nullptr, 3, dS, dCol, ncolor, voxel_size, -1, &V, ev.e[2]);
   if (rc != MGS_OK) return rc;
   hipEventRecord(ev.e[3], nullptr);
   const int nvox = (int)V.nvox;
@@ -1570,6 +1715,158 @@ int mgs_scan_cloud(int device, const mgs_scan_scene* scene, int nview, const dou
     out_stats[4] = m;
     out_stats[5] = (int64_t)n;
   }
+  return MGS_OK;
+}
+
+int mgs_scan_fps_order(int ncloud, const int64_t* n, const int32_t* k, int32_t* order) {
+  if (ncloud < 0) return fail(MGS_EINVAL, "mgs_scan_fps_order: negative size%s");
+  if (ncloud > 0 && (!n || !k || !order)) return fail(MGS_EINVAL, "mgs_scan_fps_order: null argument%s");
+  cloud_fps_order(ncloud, n, k, order);
+  return MGS_OK;
+}
+
+int mgs_scan_fps_batch(int device, int ncloud, const double* points, const int64_t* off, const int32_t* k,
+                       double bucket_size, int32_t* out_idx, int64_t* out_nevals, double* kernel_ms) {
+  const char* E = "mgs_scan_fps_batch";
+  if (ncloud < 0) return fail(MGS_EINVAL, "mgs_scan_fps_batch: negative size%s");
+  if (!cloud_size_ok(bucket_size))
+    return fail(MGS_EINVAL, "mgs_scan_fps_batch: bucket_size must be positive and finite%s");
+  if (ncloud == 0) return MGS_OK;
+  if (!off || !k) return fail(MGS_EINVAL, "mgs_scan_fps_batch: null argument%s");
+  if (off[0] != 0) return fail(MGS_EINVAL, "mgs_scan_fps_batch: off[0] must be 0%s");
+  size_t ktot = 0;
+  // first the offsets alone: only under ascending ones does every cloud lie inside points[0 .. 3 off[ncloud])
+  for (int c = 0; c < ncloud; c++)
+    if (off[c + 1] < off[c]) return fail_at(fail(MGS_EINVAL, "off must ascend%s"), E, "cloud", c);
+  for (int c = 0; c < ncloud; c++) {
+    if (int rc = scan_fps_check(points ? points + 3 * off[c] : nullptr, off[c + 1] - off[c], k[c], bucket_size, out_idx))
+      return fail_at(rc, E, "cloud", c);
+    ktot += (size_t)k[c];
+  }
+  if (ktot == 0) {
+    if (out_nevals) for (int c = 0; c < ncloud; c++) out_nevals[c] = 0;
+    return MGS_OK;
+  }
+  HIPCHK(hipSetDevice(device));
+  DevBufs b;      // the points, the outputs and every cloud's pick set-up: until the pick has run
+  double* dX = upload(b, points, 3 * (size_t)off[ncloud]);
+  int32_t* dO = b.get<int32_t>(ktot);
+  cloud_u64* dEv = b.get<cloud_u64>((size_t)ncloud);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
+  HIPCHK(hipMemsetAsync(dEv, 0, (size_t)ncloud * sizeof(cloud_u64), nullptr));
+  EvTimer t;
+  std::vector<CloudFpsJob> jobs;
+  std::vector<int64_t> ns;
+  size_t koff = 0;
+  for (int c = 0; c < ncloud; c++) {
+    if (k[c] == 0) continue;
+    DevBufs s;      // this cloud's set-up scratch (its cell grid): released before the next cloud
+    CloudFpsJob J;
+    const int64_t n = off[c + 1] - off[c];
+    int rc = cloud_fps_setup(s, b, dX + 3 * off[c], (int)n, k[c], bucket_size, dO + koff, dEv + c, &J);
+    if (rc == MGS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(MGS_EHIP, "HIP error in the pick's set-up%s");
+    if (rc != MGS_OK) return fail_at(rc, E, "cloud", c);
+    jobs.push_back(J);
+    ns.push_back(n);
+    koff += (size_t)k[c];
+  }
+  int rc = cloud_fps_launch_batch(b, jobs, ns, nullptr);
+  if (rc != MGS_OK) return rc;
+  rc = t.finish(kernel_ms);
+  if (rc != MGS_OK) return rc;
+  std::vector<cloud_u64> ev((size_t)ncloud);
+  HIPCHK(hipMemcpy(ev.data(), dEv, (size_t)ncloud * sizeof(cloud_u64), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out_idx, dO, ktot * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (out_nevals) for (int c = 0; c < ncloud; c++) out_nevals[c] = (int64_t)ev[c];
+  return MGS_OK;
+}
+
+int mgs_scan_cloud_job_size(void) { return (int)sizeof(mgs_scan_cloud_job); }
+
+int mgs_scan_cloud_batch(int device, int njob, mgs_scan_cloud_job* jobs, int nview, const double* cam_pos,
+                         const double* cam_rot, int width, int height, double fx, double fy, double cx, double cy,
+                         const double* extrinsics, double pfx, double pfy, double pcx, double pcy, int erode_iters,
+                         const double* region, double voxel_size, double* pick_ms) {
+  const char* E = "mgs_scan_cloud_batch";
+  if (njob < 0) return fail(MGS_EINVAL, "mgs_scan_cloud_batch: negative size%s");
+  CloudBatchViews v;
+  if (int rc = scan_cloud_check_views(E, nview, cam_pos, cam_rot, width, height, fx, fy, extrinsics, pfx, pfy, erode_iters,
+                                      voxel_size, &v.n))
+    return rc;
+  if (njob == 0) return MGS_OK;
+  if (!jobs) return fail(MGS_EINVAL, "mgs_scan_cloud_batch: null argument%s");
+  for (int j = 0; j < njob; j++)
+    if (int rc = scan_cloud_check_scene(jobs[j].scene, jobs[j].colors, jobs[j].ncolor, jobs[j].num_points,
+                                        jobs[j].out_points, jobs[j].out_colors))
+      return fail_at(rc, E, "job", j);
+  if (v.n == 0) {
+    for (int j = 0; j < njob; j++) {
+      jobs[j].out_n = 0;
+      for (int i = 0; i < 8; i++) jobs[j].out_stats[i] = 0;
+      for (int i = 0; i < 3; i++) jobs[j].stage_ms[i] = 0.0;
+    }
+    if (pick_ms) *pick_ms = 0.0;
+    return MGS_OK;
+  }
+  HIPCHK(hipSetDevice(device));
+  const size_t n = v.n;
+  v.nview = nview, v.width = width, v.height = height, v.erode_iters = erode_iters;
+  v.fx = fx, v.fy = fy, v.cx = cx, v.cy = cy, v.pfx = pfx, v.pfy = pfy, v.pcx = pcx, v.pcy = pcy;
+  v.voxel_size = voxel_size;
+  v.rg = region ? region : ref_region;
+  DevBufs b;      // until the pick has run: the cameras, the images, every scene's voxels and pick set-up
+  v.dCP = upload(b, cam_pos, 3 * (size_t)nview);
+  v.dCR = upload(b, cam_rot, 9 * (size_t)nview);
+  v.dE = upload(b, extrinsics, 16 * (size_t)nview);
+  v.dD = b.get<double>(n);
+  v.dD32 = b.get<double>(n);
+  v.dS = b.get<int32_t>(n);
+  v.dT = b.get<int32_t>(n);
+  v.dN = b.get<int32_t>(n);
+  v.dP = b.get<double>(3 * n);
+  v.dK = b.get<uint8_t>(n);
+  cloud_u64* dEv = b.get<cloud_u64>((size_t)njob);
+  if (!b.ok) return fail(MGS_ENOMEM, "device allocation or upload failed%s");
+  HIPCHK(hipMemsetAsync(dEv, 0, (size_t)njob * sizeof(cloud_u64), nullptr));
+  std::vector<CloudBatchScene> held((size_t)njob);
+  std::vector<CloudFpsJob> picks;
+  std::vector<int64_t> pick_n;
+  for (int j = 0; j < njob; j++) {
+    bool picked = false;
+    CloudFpsJob J;
+    if (int rc = cloud_batch_scene(b, v, jobs[j], dEv + j, &held[j], &picked, &J)) return fail_at(rc, E, "job", j);
+    if (picked) {
+      picks.push_back(J);
+      pick_n.push_back((int64_t)held[j].V.nvox);
+    }
+  }
+  double ms = 0.0;
+  if (int rc = cloud_fps_launch_batch(b, picks, pick_n, &ms)) return rc;
+  for (int j = 0; j < njob; j++) {
+    const CloudBatchScene& h = held[j];
+    if (h.m > 0)
+      hipLaunchKernelGGL(cloud_gather_kernel, dim3((h.m + MGS_CLOUD_BLOCK - 1) / MGS_CLOUD_BLOCK), dim3(MGS_CLOUD_BLOCK), 0,
+                         nullptr, h.dIdx, h.m, h.V.vpts, h.V.vfeat, h.oP, h.oC);
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<cloud_u64> evals((size_t)njob);
+  HIPCHK(hipMemcpy(evals.data(), dEv, (size_t)njob * sizeof(cloud_u64), hipMemcpyDeviceToHost));
+  // every job has succeeded: only now is anything of the caller's written
+  for (int j = 0; j < njob; j++) {
+    const CloudBatchScene& h = held[j];
+    if (h.m > 0) {
+      HIPCHK(hipMemcpy(jobs[j].out_points, h.oP, 3 * (size_t)h.m * sizeof(float), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(jobs[j].out_colors, h.oC, 3 * (size_t)h.m * sizeof(float), hipMemcpyDeviceToHost));
+    }
+  }
+  for (int j = 0; j < njob; j++) {
+    const CloudBatchScene& h = held[j];
+    jobs[j].out_n = h.m;
+    const int64_t stats[8] = {h.V.npts, h.V.nvox, (int64_t)evals[j], h.V.ncell, h.m, (int64_t)n, 0, 0};
+    for (int i = 0; i < 8; i++) jobs[j].out_stats[i] = stats[i];
+    for (int i = 0; i < 3; i++) jobs[j].stage_ms[i] = h.ms[i];
+  }
+  if (pick_ms) *pick_ms = ms;
   return MGS_OK;
 }
 

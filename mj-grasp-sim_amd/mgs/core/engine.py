@@ -95,6 +95,14 @@ def load_library(wide: bool = False):
     L.mgs_scan_cloud.argtypes = [ctypes.c_int, P(abi.ScanScene), ctypes.c_int, P(c_d), P(c_d), ctypes.c_int,
                                  ctypes.c_int, c_d, c_d, c_d, c_d, P(c_d), c_d, c_d, c_d, c_d, ctypes.c_int, P(c_d),
                                  P(c_f), ctypes.c_int, c_d, ctypes.c_int, P(c_f), P(c_f), P(c_i), P(c_i64), P(c_d)]
+    L.mgs_scan_fps_order.argtypes = [ctypes.c_int, P(c_i64), P(c_i), P(c_i)]
+    L.mgs_scan_fps_batch.argtypes = [ctypes.c_int, ctypes.c_int, P(c_d), P(c_i64), P(c_i), c_d, P(c_i), P(c_i64), P(c_d)]
+    L.mgs_scan_cloud_job_size.restype = ctypes.c_int
+    L.mgs_scan_cloud_batch.argtypes = [ctypes.c_int, ctypes.c_int, P(abi.ScanCloudJob), ctypes.c_int, P(c_d), P(c_d),
+                                       ctypes.c_int, ctypes.c_int, c_d, c_d, c_d, c_d, P(c_d), c_d, c_d, c_d, c_d,
+                                       ctypes.c_int, P(c_d), c_d, P(c_d)]
+    if L.mgs_scan_cloud_job_size() != ctypes.sizeof(abi.ScanCloudJob):
+        raise EngineError(f"{os.path.basename(path)}: mgs_scan_cloud_job differs from include/mgs_gpu.h")
     L.mgs_pose_tree_size.restype = ctypes.c_int
     L.mgs_pose_cloud.argtypes = [ctypes.c_int, P(abi.PoseTree), ctypes.c_int, P(c_d), P(c_i), ctypes.c_int, P(c_d),
                                  P(c_d), ctypes.c_int, vp, P(c_d), ctypes.c_int, P(c_d)]
@@ -687,6 +695,35 @@ CLOUD_STATS = ("kept", "voxels", "pick_evals", "grid_cells", "rows", "pixels")
 CLOUD_STAGES = ("render_ms", "points_compact_ms", "voxels_ms", "pick_ms")
 
 
+def _cloud_views(cam_pos, cam_rot, extrinsics, width, height, voxel_size, region):
+    """the camera arguments of scan_cloud / scan_cloud_batch as the arrays the
+    library reads (ValueError on a wrong shape, before the library is loaded)"""
+    cp = np.ascontiguousarray(cam_pos, np.float64).reshape(-1, 3)
+    cr = np.ascontiguousarray(cam_rot, np.float64).reshape(-1, 3, 3)
+    e = np.asarray(extrinsics, np.float64)
+    if len(cp) != len(cr) or e.shape != (len(cp), 4, 4):
+        raise ValueError("one rotation and one 4 x 4 extrinsic per camera position")
+    e = np.ascontiguousarray(e)
+    if min(int(width), int(height)) < 0:
+        raise ValueError("negative size")
+    if not (np.isfinite(voxel_size) and voxel_size > 0):
+        raise ValueError("voxel_size must be positive and finite")
+    rg = None if region is None else np.ascontiguousarray(region, np.float64).reshape(-1)
+    if rg is not None and rg.shape != (6,):
+        raise ValueError("region is (lo xyz, hi xyz)")
+    return cp, cr, e, rg
+
+
+def _cloud_scene_args(colors, num_points):
+    col = np.asarray(colors)
+    if col.ndim != 2 or col.shape[1] != 3:
+        raise ValueError("colors are (ncolor, 3)")
+    num_points = int(num_points)
+    if num_points < 0:
+        raise ValueError("negative size")
+    return np.ascontiguousarray(col, np.float32), num_points
+
+
 def scan_cloud(scene_arrays, cam_pos, cam_rot, width, height, fx, fy, cx, cy, extrinsics, pfx, pfy, pcx, pcy, colors,
                num_points, voxel_size=0.002, erode_iters=5, region=None, device=0):
     """scene -> sampled cloud with every intermediate on the GPU
@@ -697,24 +734,8 @@ def scan_cloud(scene_arrays, cam_pos, cam_rot, width, height, fx, fy, cx, cy, ex
     least num_points.  Returns (points (m, 3) float32, colors (m, 3) float32,
     dict of CLOUD_STATS and CLOUD_STAGES)."""
     from mgs.scan.scene import pack_scene
-    cp = np.ascontiguousarray(cam_pos, np.float64).reshape(-1, 3)
-    cr = np.ascontiguousarray(cam_rot, np.float64).reshape(-1, 3, 3)
-    e = np.asarray(extrinsics, np.float64)
-    if len(cp) != len(cr) or e.shape != (len(cp), 4, 4):
-        raise ValueError("one rotation and one 4 x 4 extrinsic per camera position")
-    e = np.ascontiguousarray(e)
-    col = np.asarray(colors)
-    if col.ndim != 2 or col.shape[1] != 3:
-        raise ValueError("colors are (ncolor, 3)")
-    col = np.ascontiguousarray(col, np.float32)
-    num_points = int(num_points)
-    if min(int(width), int(height), num_points) < 0:
-        raise ValueError("negative size")
-    if not (np.isfinite(voxel_size) and voxel_size > 0):
-        raise ValueError("voxel_size must be positive and finite")
-    rg = None if region is None else np.ascontiguousarray(region, np.float64).reshape(-1)
-    if rg is not None and rg.shape != (6,):
-        raise ValueError("region is (lo xyz, hi xyz)")
+    cp, cr, e, rg = _cloud_views(cam_pos, cam_rot, extrinsics, width, height, voxel_size, region)
+    col, num_points = _cloud_scene_args(colors, num_points)
     L = _device_lib(device)
     scene, keep = pack_scene(scene_arrays)
     oP, oC = np.zeros((num_points, 3), np.float32), np.zeros((num_points, 3), np.float32)
@@ -731,6 +752,91 @@ def scan_cloud(scene_arrays, cam_pos, cam_rot, width, height, fx, fy, cx, cy, ex
     info = {k: int(v) for k, v in zip(CLOUD_STATS, stats)}
     info.update({k: float(v) for k, v in zip(CLOUD_STAGES, stages)})
     return oP[:n.value], oC[:n.value], info
+
+
+def scan_fps_order(ns, ks):
+    """the order in which the batched pick takes its clouds (mgs_scan_fps_order,
+    host only): descending n * k, equal work by ascending index"""
+    n = np.ascontiguousarray(ns, np.int64).reshape(-1)
+    k = np.ascontiguousarray(ks, np.int32).reshape(-1)
+    if len(n) != len(k):
+        raise ValueError("one k per cloud")
+    L = load_library()
+    order = np.zeros(len(n), np.int32)
+    _check(L.mgs_scan_fps_order(len(n), ptr(n, ctypes.c_int64), ptr(k, ctypes.c_int32), ptr(order, ctypes.c_int32)),
+           "mgs_scan_fps_order", L)
+    return order
+
+
+def scan_fps_batch(clouds, ks, bucket_size, device=0):
+    """scan_fps of many clouds with one pick launch, a workgroup per cloud
+    (mgs_scan_fps_batch): clouds is a sequence of (n_c, 3) float arrays, ks one
+    k per cloud.  Returns (list of index arrays, evaluation counts (ncloud,)
+    int64, kernel ms); per cloud exactly scan_fps's indices and count."""
+    clouds = list(clouds)
+    for x in clouds:
+        if not isinstance(x, np.ndarray) or x.dtype.kind != "f" or x.ndim != 2 or x.shape[1] != 3:
+            raise ValueError("every cloud is an (n, 3) float array")
+    k = np.asarray(ks)
+    if k.ndim != 1 or len(k) != len(clouds) or (len(k) and k.dtype.kind not in "iu"):
+        raise ValueError("ks holds one integer per cloud")
+    k = np.ascontiguousarray(k, np.int32)
+    n = np.array([len(x) for x in clouds], np.int64)
+    if np.any(k < 0) or np.any(k > n):
+        raise ValueError("need 0 <= k <= n for every cloud")
+    if not (np.isfinite(bucket_size) and bucket_size > 0):
+        raise ValueError("bucket_size must be positive and finite")
+    off = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    koff = np.concatenate([[0], np.cumsum(k, dtype=np.int64)])
+    x = np.ascontiguousarray(np.concatenate(clouds) if clouds else np.zeros((0, 3)), np.float64)
+    L = _device_lib(device)
+    out = np.zeros(int(koff[-1]), np.int32)
+    nev, ms = np.zeros(len(clouds), np.int64), ctypes.c_double(0.0)
+    _check(L.mgs_scan_fps_batch(device, len(clouds), ptr(x, ctypes.c_double), ptr(off, ctypes.c_int64),
+                                ptr(k, ctypes.c_int32), float(bucket_size), ptr(out, ctypes.c_int32),
+                                ptr(nev, ctypes.c_int64), ctypes.byref(ms)), "mgs_scan_fps_batch", L)
+    return [out[koff[c]:koff[c + 1]] for c in range(len(clouds))], nev, ms.value
+
+
+def scan_cloud_batch(scenes, colors, num_points, cam_pos, cam_rot, width, height, fx, fy, cx, cy, extrinsics, pfx, pfy,
+                     pcx, pcy, voxel_size=0.002, erode_iters=5, region=None, device=0):
+    """scan_cloud of many scenes seen by the same cameras (mgs_scan_cloud_batch):
+    render, points and voxels scene after scene, then the picks of all scenes
+    in one launch.  scenes: a sequence of scene_arrays; colors: one (ncolor, 3)
+    table per scene; num_points: one count for all or one per scene.  Returns a
+    list of (points, colors, info) as scan_cloud's, info["pick_ms"] being the
+    shared launch's time."""
+    from mgs.scan.scene import pack_scene
+    scenes, colors = list(scenes), list(colors)
+    nums = [num_points] * len(scenes) if np.ndim(num_points) == 0 else list(num_points)
+    if len(colors) != len(scenes) or len(nums) != len(scenes):
+        raise ValueError("one colour table and one num_points per scene")
+    cp, cr, e, rg = _cloud_views(cam_pos, cam_rot, extrinsics, width, height, voxel_size, region)
+    per = [_cloud_scene_args(c, m) for c, m in zip(colors, nums)]
+    L = _device_lib(device)
+    jobs = (abi.ScanCloudJob * max(len(scenes), 1))()
+    alive = []                      # what the job records point into
+    for j, (arrays, (col, m)) in enumerate(zip(scenes, per)):
+        scene, keep = pack_scene(arrays)
+        oP, oC = np.zeros((m, 3), np.float32), np.zeros((m, 3), np.float32)
+        alive.append((scene, keep, col, oP, oC))
+        jobs[j].scene = ctypes.pointer(scene)
+        jobs[j].colors = ptr(col, ctypes.c_float)
+        jobs[j].ncolor, jobs[j].num_points = len(col), m
+        jobs[j].out_points, jobs[j].out_colors = ptr(oP, ctypes.c_float), ptr(oC, ctypes.c_float)
+    d = ctypes.c_double
+    pick = d(0.0)
+    _check(L.mgs_scan_cloud_batch(device, len(scenes), jobs, len(cp), ptr(cp, d), ptr(cr, d), int(width), int(height),
+                                  float(fx), float(fy), float(cx), float(cy), ptr(e, d), float(pfx), float(pfy),
+                                  float(pcx), float(pcy), int(erode_iters), None if rg is None else ptr(rg, d),
+                                  float(voxel_size), ctypes.byref(pick)), "mgs_scan_cloud_batch", L)
+    out = []
+    for j, (_, _, _, oP, oC) in enumerate(alive):
+        info = {k: int(v) for k, v in zip(CLOUD_STATS, jobs[j].out_stats)}
+        info.update({k: float(v) for k, v in zip(CLOUD_STAGES[:3], jobs[j].stage_ms)})
+        info["pick_ms"] = pick.value
+        out.append((oP[:jobs[j].out_n], oC[:jobs[j].out_n], info))
+    return out
 
 
 def contact_seeds(seeds, radius, rng_seed, ntip, device=0):

@@ -704,6 +704,17 @@ class ClutterTableEnv:
         self.last_scan = res
         return rgbd, extr, erode_mask(seg != -1, 5), seg
 
+    def _cloud_cameras(self, num_images, width, height):
+        """(extrinsics (N, 4, 4), render intrinsics, point intrinsics) of the
+        views scan_cloud takes; sets the image size as scan does"""
+        self.scan_width, self.scan_height = int(width), int(height)
+        extr = []
+        for i in range(num_images):
+            self.update_camera_settings(num_images, i)
+            extr.append(self.get_camera_extrinsics())
+        extr = np.stack(extr, axis=0) if extr else np.zeros((0, 4, 4))
+        return extr, self.get_render_intrinsics(), self.get_camera_intrinsics()
+
     def scan_cloud(self, num_images, num_points=15000, voxel_size=0.002, width=480, height=480):
         """the cloud render_scene_processed writes, with everything between the
         scene and the sampled points on the GPU (mgs_scan_cloud): the views of
@@ -714,13 +725,7 @@ class ClutterTableEnv:
         (mgs.core.engine.CLOUD_STATS, CLOUD_STAGES)."""
         from mgs.core.engine import scan_cloud
         from mgs.scan.scene import REGION
-        self.scan_width, self.scan_height = int(width), int(height)
-        extr = []
-        for i in range(num_images):
-            self.update_camera_settings(num_images, i)
-            extr.append(self.get_camera_extrinsics())
-        extr = np.stack(extr, axis=0) if extr else np.zeros((0, 4, 4))
-        K, Kp = self.get_render_intrinsics(), self.get_camera_intrinsics()
+        extr, K, Kp = self._cloud_cameras(num_images, width, height)
         points, colors, info = scan_cloud(self.scan_scene().arrays(), extr[:, :3, 3], extr[:, :3, :3], width, height,
                                           K[0, 0], K[1, 1], K[0, 2], K[1, 2], extr, Kp[0, 0], Kp[1, 1], Kp[0, 2],
                                           Kp[1, 2], self.scan_colors(), num_points, voxel_size=voxel_size,
@@ -737,3 +742,32 @@ class ClutterTableEnv:
             c[0] = np.asarray(self.table_rgba, np.float64)[:3]
         c[1] = [1.0, 0.0, 0.0]
         return c
+
+
+def scan_clouds(envs, num_images, num_points=15000, voxel_size=0.002, width=480, height=480, batch=64):
+    """[env.scan_cloud(num_images, num_points, voxel_size, width, height) for env
+    in envs], bit for bit, with the farthest-point picks of up to `batch` scenes
+    in one launch (mgs_scan_cloud_batch: a workgroup per scene).  Every env's
+    `last_cloud` is set; its pick_ms is the shared launch's.  The envs see their
+    piles through the same cameras, so they must live on one device."""
+    from mgs.core.engine import scan_cloud_batch
+    from mgs.scan.scene import REGION
+    envs = list(envs)
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError("batch must be at least 1")
+    if len({e.device for e in envs}) > 1:
+        raise ValueError("scan_clouds: the envs live on different devices")
+    out = []
+    for lo in range(0, len(envs), batch):
+        chunk = envs[lo:lo + batch]
+        # the views depend on num_images and the image size alone: every env's are the first one's
+        extr, K, Kp = [e._cloud_cameras(num_images, width, height) for e in chunk][0]
+        res = scan_cloud_batch([e.scan_scene().arrays() for e in chunk], [e.scan_colors() for e in chunk], num_points,
+                               extr[:, :3, 3], extr[:, :3, :3], width, height, K[0, 0], K[1, 1], K[0, 2], K[1, 2], extr,
+                               Kp[0, 0], Kp[1, 1], Kp[0, 2], Kp[1, 2], voxel_size=voxel_size, erode_iters=5,
+                               region=REGION, device=chunk[0].device)
+        for e, (points, colors, info) in zip(chunk, res):
+            e.last_cloud = info
+            out.append((points, colors))
+    return out
